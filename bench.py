@@ -10,7 +10,13 @@ GPU count; ranks take contiguous index ranges (weak scaling, no data-path
 collective; one all_reduce of counters + max elapsed at the end).
 
 python bench.py [--gpus N --steps K --warmup W] [--alg ML-KEM-768] [--log2-batch 20]
-                [--mode encdec|decaps-tampered] [--no-cpu]
+                [--mode encdec|decaps-tampered] [--dump-outputs DIR] [--full [--no-cpu]]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own: the kernel-in-isolation pass (`kernels`, `roofline.isolated_frac`), the
+all-valid / all-tampered Decaps timings of decaps-tampered mode, and the CPU baseline with its
+byte-for-byte check of a sample of the GPU outputs (`cpu_baseline`).  --dump-outputs DIR writes what
+the last timed step returned as DIR/<name>.npy (float32; a fixed, seeded sample of the rows): ct, ss
+and ss_decaps, or ss_decaps alone in decaps-tampered mode, where the timed step is the Decaps.
 For N > 1 bench.py either runs under torch.distributed.run (one rank per GPU, RCCL backend) or,
 started directly with --gpus N, launches the N ranks itself as a child process and relays rank 0's
 line.
@@ -269,6 +275,28 @@ RED_DEVICE = None  # device of the end-of-run reduction tensors (None = host, fo
 def env_int(name, default):
     v = os.environ.get(name)
     return int(v) if v not in (None, "") else default
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 over all dumped arrays (the files stay below 64 MB in all)
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(dirname, named):
+    """--dump-outputs: write the row-aligned tensors `named` (what the last timed step returned) as
+    <dirname>/<name>.npy in float32.  Outputs too large for DUMP_BUDGET are sampled by row: the same
+    sorted rows of every array, drawn once from DUMP_SEED (rows.npy, float64, holds their indices),
+    so that two runs with the same arguments write the same rows."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    named = {k: (t if t.dim() > 1 else t.reshape(-1, 1)) for k, t in named.items()}
+    n = min(t.shape[0] for t in named.values())
+    per_row = 4 * sum(t[0].numel() for t in named.values()) + 8
+    keep = max(1, min(n, DUMP_BUDGET // per_row))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False)) if keep < n else np.arange(n)
+    np.save(d / "rows.npy", rows.astype(np.float64))
+    for name, t in named.items():
+        idx = torch.from_numpy(rows).to(t.device)
+        np.save(d / f"{name}.npy", t[idx].cpu().numpy().astype(np.float32))
 
 
 def host_cpu() -> dict:
@@ -579,6 +607,10 @@ def bench_handshake(args, world, rank, local):
     elapsed = time.perf_counter() - t0
     prof = e.profile_read() if not args.no_profile else {}
     e.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pk_initiator": out.pk_initiator, "pk_responder": out.pk_responder,
+                                         "ciphertext": out.ciphertext, "key_initiator": out.key_initiator,
+                                         "key_responder": out.key_responder, "agree": out.agree})
     disagree = int((out.agree != 1).sum().item())
     elapsed, (disagree,) = reduce_run(elapsed, [disagree], device=RED_DEVICE)
     value = B * world * args.steps / elapsed
@@ -609,7 +641,7 @@ def bench_handshake(args, world, rank, local):
         "roofline": roof, "valu_frac_of_peak_step": value * W / (VALU_PEAK * world) if W else None, "valu_ops_per_unit": W,
         "kernels_timed_region": kernels, "checks": {"key_disagreements": disagree}, "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         sys.path.insert(0, str(ROOT / "oracle"))
         import oracle as orc
         threads = cpu_threads()
@@ -686,6 +718,10 @@ def bench_wire(args, world, rank, local):
     elapsed = time.perf_counter() - t0
     prof = _ctx_profile_read(codec) if not args.no_profile else {}
     t_pk, t_ct, t_pkr, pk_rx, ct_rx, st1, st2 = out
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pk_initiator_b64": t_pk, "ciphertext_b64": t_ct, "pk_responder_b64": t_pkr,
+                                         "pk_initiator_decoded": pk_rx, "ciphertext_decoded": ct_rx,
+                                         "pk_initiator_status": st1, "ciphertext_status": st2})
     bad = int((pk_rx != pk_i).any(dim=1).sum().item() + (ct_rx != ct_).any(dim=1).sum().item()
               + st1.abs().sum().item() + st2.abs().sum().item())
     elapsed, (bad,) = reduce_run(elapsed, [bad], device=RED_DEVICE)
@@ -719,7 +755,7 @@ def bench_wire(args, world, rank, local):
         "roofline": roof, "hbm_GBs_step": value * bytes_hs / 1e9, "kernels_timed_region": kernels,
         "checks": {"roundtrip_mismatches_or_rejects": bad}, "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         import base64
         S = 1 << 14
         h_pk, h_pkr, h_ct = (np.ascontiguousarray(t[:S].cpu().numpy()) for t in (pk_i, pk_r, ct_))
@@ -841,9 +877,18 @@ def main():
     ap.add_argument("--streams", type=int, default=0, choices=[0, 1],
                     help="library schedule (qrk_ctx_set_streams): 0 multi-role launches, 1 serial "
                          "(one kernel per launch); every kernel runs on the caller's stream in both")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the kernel-in-isolation pass, the "
+                         "all-valid / all-tampered Decaps timings (decaps-tampered mode) and the CPU baseline "
+                         "with its check of a sample of the GPU outputs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, a fixed seeded "
+                         "sample of the rows; rank 0's shard)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-profile", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps: at least one timed step")
 
     if args.global_log2_batch is not None and (1 << args.global_log2_batch) < args.gpus:
         raise SystemExit(f"--global-log2-batch {args.global_log2_batch}: fewer handshakes than ranks")
@@ -947,7 +992,7 @@ def main():
             eng.tamper(c, args.seed, m)
             cts[name] = c
         torch.cuda.synchronize()
-        for name in ("all-valid", "all-tampered"):
+        for name in ("all-valid", "all-tampered") if args.full else ():
             el, _ = timed(lambda c=cts[name]: eng.decaps(sk, c))
             variants[name] = el * 1e3 / args.steps
 
@@ -961,7 +1006,7 @@ def main():
     # one kernel per launch, the SampleNTT fix-up included), since the multi-role launches of the
     # timed region time two kernels as one.
     prof = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         eng.set_streams(1)
         eng.profile(True)
         main_step()
@@ -971,6 +1016,10 @@ def main():
         eng.set_streams(args.streams)
 
     ct, ss, ss2 = out
+    if args.dump_outputs and rank == 0:
+        # decaps-tampered: the timed step is Decaps alone; ct and ss there are its untimed inputs
+        dump_outputs(args.dump_outputs, {"ct": ct, "ss": ss, "ss_decaps": ss2} if args.mode == "encdec" else
+                     {"ss_decaps": ss2})
     if args.mode == "encdec":
         bad = int((ss != ss2).any(dim=1).sum().item())
         counters = [bad, 0]
@@ -991,7 +1040,8 @@ def main():
         checks["implicit_rejection_mismatches"] = bad
         checks["tampered"] = n_tampered
         checks["decaps_ms_per_step"] = variants
-        checks["tampered_over_valid_time"] = variants["all-tampered"] / variants["all-valid"]
+        if args.full:
+            checks["tampered_over_valid_time"] = variants["all-tampered"] / variants["all-valid"]
 
     total = (1 << lb if strong else B * world) * args.steps
     value = total / elapsed
@@ -1079,7 +1129,7 @@ def main():
                              "SHA-256 over each rank's record digests (depends on the GPU count)"),
             "blocks": {str(k): v for k, v in sorted(allb.items())},
             "global": combine_digests(allb), "rank0_blocks": sorted(mine)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(alg, args.mode, kc, pk, sk, ec, ct, ss2 if args.mode != "encdec" else ss,
                                               B)
     if rank == 0:

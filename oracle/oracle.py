@@ -1,7 +1,7 @@
 """ctypes wrapper around oracle/liboracle.so -- TEST INFRASTRUCTURE ONLY.
 
 The parity oracle for the batched KEM engine.  Only ``tests/``,
-``__graft_entry__.smoke()`` (as the checker) and ``bench.py``'s cpu_baseline leg
+``__graft_entry__.smoke()`` (as the checker) and ``bench.py --full``'s cpu_baseline leg
 import this module; the product path (``quantum-resistant-p2p_amd/qrkem``) never
 does, and fails loudly when its HIP library is missing instead of falling back
 here.

@@ -3,6 +3,7 @@ and answers the registry / struct queries the reference's ctypes wrapper makes
 (quantum_resistant_p2p/vendor/oqs.py:192-198, 241-253, 271-280, 396-421).
 No KEM compute is called here unless a GPU is present."""
 import ctypes as ct
+import json
 import re
 import subprocess
 from pathlib import Path
@@ -125,6 +126,85 @@ def test_encap_secret_length_semantics():
     k = oqs.KeyEncapsulation("ML-KEM-512")
     with pytest.raises(ValueError):
         k.encap_secret(bytes(801))
+
+
+@pytest.fixture(scope="module")
+def dropin(golden_dir):
+    """What the reference's unmodified ctypes wrapper and KEM plugins reported when they ran over
+    libqrkem.so in place of liboqs.so (tests/golden/make_dropin_fixture.py; outputs only)."""
+    return json.loads((golden_dir / "dropin.json").read_text())
+
+
+def test_library_answers_as_recorded_for_the_reference_wrapper(dropin):
+    """The registry, version and OQS_KEM struct values the wrapper read are what the library says
+    through include/qrkem.h, and the names the wrapper refused get NULL from OQS_KEM_new."""
+    from qrkem._native import LIB
+    assert LIB.OQS_version().decode() == dropin["version"] and "qrkem" in dropin["version"]
+    ids = [LIB.OQS_KEM_alg_identifier(i).decode() for i in range(LIB.OQS_KEM_alg_count())]
+    assert ids == dropin["supported"]
+    assert [n for n in ids if LIB.OQS_KEM_alg_is_enabled(n.encode()) == 1] == dropin["enabled"]
+    assert {"ML-KEM-512", "ML-KEM-768", "ML-KEM-1024"} <= set(dropin["enabled"])
+    assert LIB.OQS_SIG_alg_count() == len(dropin["enabled_sigs"]) == 0
+    assert sorted(dropin["details"]) == sorted(dropin["enabled"])
+    for alg, det in dropin["details"].items():
+        p = LIB.OQS_KEM_new(alg.encode())
+        assert p, alg
+        s = ct.cast(p, ct.POINTER(OQSKemStruct)).contents
+        assert {"name": s.method_name.decode(), "version": s.alg_version.decode(),
+                "claimed_nist_level": s.claimed_nist_level, "is_ind_cca": bool(s.ind_cca),
+                "length_public_key": s.length_public_key, "length_secret_key": s.length_secret_key,
+                "length_ciphertext": s.length_ciphertext, "length_shared_secret": s.length_shared_secret} == det
+        assert s.keypair_cb and s.encaps_cb and s.decaps_cb
+        LIB.OQS_KEM_free(p)
+    assert dropin["details"]["ML-KEM-768"]["length_public_key"] == 1184
+    assert dropin["details"]["HQC-128"]["length_ciphertext"] == 4433
+    assert set(dropin["refused"]) >= {"BIKE-L1", "Kyber768"}
+    for alg, exc in dropin["refused"].items():
+        assert exc == "MechanismNotSupportedError"
+        assert not LIB.OQS_KEM_new(alg.encode()) and alg not in ids
+
+
+def test_single_shot_calls_as_recorded_without_a_device_or_round_trip(dropin):
+    """Without a GPU the wrapper saw every single-shot call fail (recorded); the library returns
+    OQS_ERROR with the recorded message and qrkem's plugins raise what the reference's did.  With
+    a GPU the same calls complete a KeyGen / Encaps / Decaps round trip."""
+    import qrkem
+    from qrkem import key_exchange as ke
+    from qrkem._native import LIB
+    assert dropin["no_device"]["generate_keypair"] == "RuntimeError: Can not generate keypair"
+    assert dropin["no_device"]["encap_secret"] == "RuntimeError: Can not encapsulate secret"
+    assert dropin["no_device"]["decap_secret"] == "RuntimeError: Can not decapsulate secret"
+    alg = "ML-KEM-1024"
+    det = dropin["details"][alg]
+    p = LIB.OQS_KEM_new(alg.encode())
+    pk, sk = ct.create_string_buffer(det["length_public_key"]), ct.create_string_buffer(det["length_secret_key"])
+    c, ss = ct.create_string_buffer(det["length_ciphertext"]), ct.create_string_buffer(det["length_shared_secret"])
+    ss2 = ct.create_string_buffer(det["length_shared_secret"])
+    if qrkem.device_count() == 0:
+        assert LIB.OQS_KEM_keypair(p, pk, sk) == -1
+        assert qrkem.last_error() == dropin["no_device"]["last_error"]
+        assert LIB.OQS_KEM_encaps(p, c, ss, pk) == -1
+        assert LIB.OQS_KEM_decaps(p, ss2, c, sk) == -1
+    else:
+        assert LIB.OQS_KEM_keypair(p, pk, sk) == 0
+        assert LIB.OQS_KEM_encaps(p, c, ss, pk) == 0
+        assert LIB.OQS_KEM_decaps(p, ss2, c, sk) == 0
+        assert ss.raw == ss2.raw and ss.raw != bytes(len(ss.raw))
+    LIB.OQS_KEM_free(p)
+    assert len(dropin["plugins"]) == 12
+    for row in dropin["plugins"]:
+        obj = getattr(ke, row["cls"])(**row["kwargs"])
+        assert (obj.name, obj.variant) == (row["name"], row["variant"])
+        assert row["generate_keypair"] == "RuntimeError: Can not generate keypair"
+    plug = ke.MLKEMKeyExchange(5)
+    assert plug.variant == "ML-KEM-1024" and plug.name == "ML-KEM (Level 5)"
+    if qrkem.device_count() == 0:
+        with pytest.raises(RuntimeError, match="^Can not generate keypair$"):
+            plug.generate_keypair()
+    else:
+        pk_b, sk_b = plug.generate_keypair()
+        c_b, ss_b = plug.encapsulate(pk_b)
+        assert plug.decapsulate(sk_b, c_b) == ss_b
 
 
 LEVELS = {"ML-KEM-512": 1, "ML-KEM-768": 3, "ML-KEM-1024": 5, "FrodoKEM-640-AES": 1, "FrodoKEM-640-SHAKE": 1,

@@ -43,7 +43,7 @@ smoke() {
 
 bench() {
   local tag=$1; shift
-  timeout -k 10 ${BENCH_TIMEOUT:-400} python3 "$R/bench.py" "$@" > "$O/$tag.json" 2> "$O/$tag.err"
+  timeout -k 10 ${BENCH_TIMEOUT:-400} python3 "$R/bench.py" ${BENCH_FULL:+--full} "$@" > "$O/$tag.json" 2> "$O/$tag.err"
   local rc=$?
   echo "bench $tag rc=$rc"
   return $rc
@@ -51,14 +51,16 @@ bench() {
 
 _ab_one() {  # tag, bench args...
   local t=$1; shift
-  local lib= py=$R/bench.py
+  local lib= py=$R/bench.py full=--full  # --full: the serial-schedule `kernels` table read below
   case "$t" in
     default) lib=$R/quantum-resistant-p2p_amd/qrkem/libqrkem.so ;;
-    tree:*) py=$R/${t#tree:}/bench.py; lib=$R/${t#tree:}/quantum-resistant-p2p_amd/qrkem/libqrkem.so ;;
+    tree:*) py=$R/${t#tree:}/bench.py; lib=$R/${t#tree:}/quantum-resistant-p2p_amd/qrkem/libqrkem.so
+            # an older tree's bench.py has no --full and always runs that pass
+            python3 "$py" --help 2>/dev/null | grep -q -e '--full' || full= ;;
     *) lib=$R/quantum-resistant-p2p_amd/qrkem/variants/libqrkem_$t.so ;;
   esac
   local o
-  o=$(QRKEM_LIBRARY=$lib timeout -k 10 ${AB_TIMEOUT:-240} python3 "$py" --no-cpu "$@" 2>>"$O/ab.err") || return 1
+  o=$(QRKEM_LIBRARY=$lib timeout -k 10 ${AB_TIMEOUT:-240} python3 "$py" $full --no-cpu "$@" 2>>"$O/ab.err") || return 1
   python3 -c "
 import json,sys
 d=json.loads(sys.argv[2])
@@ -110,7 +112,7 @@ prof() {
   mkdir -p "$d"
   ( export TMPDIR=/tmp; cd /tmp &&
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$d/trace" -o run -- \
-      python3 "$R/bench.py" --steps ${PROF_STEPS:-5} --warmup ${PROF_WARMUP:-1} --no-cpu "$@" \
+      python3 "$R/bench.py" --steps ${PROF_STEPS:-5} --warmup ${PROF_WARMUP:-1} --full --no-cpu "$@" \
       > "$d/bench_trace.json" 2> "$d/trace.err" &&
     timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$d/fetch" -o run -- \
       python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu --no-profile "$@" > "$d/bench_fetch.json" 2> "$d/fetch.err" &&
@@ -181,6 +183,7 @@ run() {
 
 # sweep: one bench line (CPU baseline included) for every BASELINE.json config and SURVEY 8f mode
 sweep() {
+  local BENCH_FULL=1  # bench.py --full: the serial-schedule kernels table and the CPU baseline
   bench mlkem768 && bench mlkem512 --alg ML-KEM-512 && bench mlkem1024 --alg ML-KEM-1024 &&
   bench mlkem1024_tampered --alg ML-KEM-1024 --mode decaps-tampered &&
   bench mlkem768_2p24 --global-log2-batch 24 --steps 3 --warmup 1 &&
