@@ -191,6 +191,14 @@ int qrk_digest_rows(qrk_ctx *ctx, size_t n, const uint8_t *a, size_t a_len, cons
  * [n][weight] each. */
 int qrk_hqc_supports(qrk_ctx *ctx, const char *alg, int kind, size_t n, const uint32_t *r, uint32_t *sup,
                      void *stream);
+/* HQC concatenated-code decoder alone (the first stages of Decaps, exposed so the decoder can be
+ * tested on chosen inputs: with u = 0 in ct the decoded word is v itself): for each of n records,
+ * syms[i] = the n1 Reed-Muller symbols decoded from v - u y, mprime[i] = the k message bytes the
+ * Reed-Solomon decoder returns for them.  No re-encryption, no shared secret.  Device pointers:
+ * sk [n][sk_len], ct [n][ct_len], syms [n][n1], mprime [n][k].  n must not exceed the context's
+ * chunk for the algorithm (qrk_ctx_effective_chunk). */
+int qrk_hqc_code_decode(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *ct,
+                        uint8_t *syms, uint8_t *mprime, void *stream);
 
 /* HKDF-SHA256 (RFC 5869) over n keys, one GPU lane per key.  Replaces
  * SecureMessaging._derive_symmetric_key (messaging.py:350-382: HKDF(SHA256,

@@ -203,7 +203,9 @@ def code_encode(p: dict, msg: bytes) -> int:
     return v
 
 
-def rm_decode_symbol(bits: int, mult: int) -> int:
+def rm_hadamard(bits: int, mult: int) -> list[int]:
+    """The 128 correlation values the RM decoder compares (transform of the summed copies,
+    entry 0 recentred)."""
     cnt = [0] * 128
     for c in range(mult):
         word = bits >> (128 * c)
@@ -218,6 +220,11 @@ def rm_decode_symbol(bits: int, mult: int) -> int:
                 t[i], t[i + h] = a + b, a - b
         h *= 2
     t[0] -= 64 * mult
+    return t
+
+
+def rm_decode_symbol(bits: int, mult: int) -> int:
+    t = rm_hadamard(bits, mult)
     best_abs, best_val, best_pos = 0, 0, 0
     for i in range(128):
         a = abs(t[i])
@@ -237,15 +244,18 @@ def _eval(poly: list[int], x: int) -> int:
     return acc
 
 
-def rs_decode(p: dict, r: list[int]) -> list[int]:
-    """Berlekamp-Massey + Chien + Forney over the n1 positions (bounded distance)."""
-    n1, t2 = p["n1"], 2 * p["delta"]
-    S = rs_syndromes(p, r)
+def rs_berlekamp_massey(S: list[int], trace: list | None = None) -> list[int]:
+    """Error locator C (t2 + 1 coefficients, low -> high) of the syndromes S_1..S_t2.  With
+    `trace`, (i, L, d) is appended for every step: the register length before the step and
+    the discrepancy (tests pick inputs by it)."""
+    t2 = len(S)
     C, B, L, m, b = [1] + [0] * t2, [1] + [0] * t2, 0, 1, 1
     for i in range(t2):
         d = S[i]
         for j in range(1, L + 1):
             d ^= gf_mul(C[j], S[i - j])
+        if trace is not None:
+            trace.append((i, L, d))
         if d == 0:
             m += 1
             continue
@@ -257,6 +267,14 @@ def rs_decode(p: dict, r: list[int]) -> list[int]:
             L, B, b, m = i + 1 - L, T, d, 1
         else:
             m += 1
+    return C
+
+
+def rs_decode(p: dict, r: list[int]) -> list[int]:
+    """Berlekamp-Massey + Chien + Forney over the n1 positions (bounded distance)."""
+    n1, t2 = p["n1"], 2 * p["delta"]
+    S = rs_syndromes(p, r)
+    C = rs_berlekamp_massey(S)
     omega = [0] * t2  # S(x) C(x) mod x^(2 delta), S(x) = sum S_{i+1} x^i
     for i in range(t2):
         for j in range(i + 1):

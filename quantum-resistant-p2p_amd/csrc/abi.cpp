@@ -1128,6 +1128,29 @@ int qrk_hqc_supports(qrk_ctx* ctx, const char* alg, int kind, size_t n, const ui
   return e == hipSuccess ? 0 : hip_fail("hqc_supports", e);
 }
 
+int qrk_hqc_code_decode(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
+                        uint8_t* mprime, void* stream) {
+  QRK_RESOLVE(ctx, alg);
+  if (a->family != Family::HQC) return fail(std::string("not an HQC parameter set: ") + alg);
+  if (n == 0) return 0;
+  if (!sk || !ct || !syms || !mprime) return fail("null buffer");
+  if (n > chunk_for(ctx, *a)) return fail("hqc_code_decode: n exceeds the context chunk");
+  hipStream_t st = (hipStream_t)stream;
+  DeviceGuard device_guard;
+  if (device_guard.set(ctx->device)) return -1;
+  if (ctx_order(ctx, st)) return -1;
+  LastUse last_use{ctx, st};
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_for(*a, (n + 63) & ~(size_t)63), st)) return -1;
+  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  g_launch_err = hipSuccess;
+  (void)hipGetLastError();
+  hipError_t e = hqc_code_decode(*a, n, sk, ct, syms, mprime, ctx->scratch, st);
+  if (e == hipSuccess) e = g_launch_err;
+  if (e != hipSuccess) return hip_fail("hqc_code_decode", e);
+  e = cleanse_records(*a, n, ctx->scratch, st);  // the symbols and m' do not outlive the call
+  return e == hipSuccess ? 0 : hip_fail("hipMemsetAsync(cleanse)", e);
+}
+
 int qrk_hkdf_sha256_batch(qrk_ctx* ctx, size_t n, const uint8_t* ikm, size_t ikm_len, const uint8_t* salt,
                           size_t salt_len, const uint8_t* info, const uint64_t* info_off, size_t info_len,
                           uint8_t* okm, size_t okm_len, void* stream) {

@@ -1374,12 +1374,10 @@ hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const
   return hipGetLastError();
 }
 
+// m' = C.decode(v - u y): RM symbols -> v.msg (row stride MW * 8), m' -> v.mp (row stride 32)
 template <int L>
-hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t* status, void* scratch,
-                    hipStream_t st) {
+void launch_code_decode(size_t n, const uint8_t* ct, const uint8_t* sk, const View& v, hipStream_t st) {
   using P = HQ<L>;
-  View v = carve<L>(scratch, n);
-  int32_t* stp = status ? status : v.st;
   if (n <= QRK_HQC_COOP_MAX)
     QRK_LAUNCH("k_hqc_dec_expand", st, k_hqc_dec_expand_c<L>, dim3((unsigned)n), dim3(64), 0, st, sk, n, v.row);
   else
@@ -1390,6 +1388,28 @@ hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
              (size_t)P::MW * 8);
   QRK_LAUNCH("k_hqc_rs", st, k_hqc_rs<L>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, (const uint8_t*)syms,
              (size_t)P::MW * 8, v.mp);
+}
+
+// (test hook behind qrk_hqc_code_decode: the decoder stages of Decaps alone, their scratch rows
+// copied out dense)
+template <int L>
+hipError_t code_decode_t(size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms, uint8_t* mprime, void* scratch,
+                         hipStream_t st) {
+  using P = HQ<L>;
+  View v = carve<L>(scratch, n);
+  launch_code_decode<L>(n, ct, sk, v, st);
+  qrk_chk(hipMemcpy2DAsync(syms, P::N1, v.msg, (size_t)P::MW * 8, P::N1, n, hipMemcpyDeviceToDevice, st));
+  qrk_chk(hipMemcpy2DAsync(mprime, P::K, v.mp, 32, P::K, n, hipMemcpyDeviceToDevice, st));
+  return hipGetLastError();
+}
+
+template <int L>
+hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t* status, void* scratch,
+                    hipStream_t st) {
+  using P = HQ<L>;
+  View v = carve<L>(scratch, n);
+  int32_t* stp = status ? status : v.st;
+  launch_code_decode<L>(n, ct, sk, v, st);
   launch_enc_expand<L>(v.mp, (size_t)32, sk + SEED + P::K, (size_t)P::SK, ct + P::NB + P::VB, (size_t)P::CT, n, v.row,
                        st);
   QRK_LAUNCH("k_hqc_enc_mul", st, (k_hqc_enc_mul<L, true>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, v.row,
@@ -1452,6 +1472,17 @@ hipError_t hqc_supports(const AlgInfo& a, int kind, size_t n, const uint32_t* r,
     case 128: return hqc::supports_t<128>(kind, n, r, sup, st);
     case 192: return hqc::supports_t<192>(kind, n, r, sup, st);
     case 256: return hqc::supports_t<256>(kind, n, r, sup, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t hqc_code_decode(const AlgInfo& a, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
+                           uint8_t* mprime, void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  switch (a.k) {
+    case 128: return hqc::code_decode_t<128>(n, sk, ct, syms, mprime, scratch, st);
+    case 192: return hqc::code_decode_t<192>(n, sk, ct, syms, mprime, scratch, st);
+    case 256: return hqc::code_decode_t<256>(n, sk, ct, syms, mprime, scratch, st);
   }
   return hipErrorInvalidValue;
 }

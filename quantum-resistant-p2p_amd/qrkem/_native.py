@@ -59,6 +59,7 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_tamper": (ct.c_int, [P, SZ, SZ, ct.c_uint64, ct.c_int, P, P]),
         "qrk_digest_rows": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P]),
         "qrk_hqc_supports": (ct.c_int, [P, ct.c_char_p, ct.c_int, SZ, P, P, P]),
+        "qrk_hqc_code_decode": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P]),
         "qrk_hkdf_sha256_batch": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P, SZ, P, SZ, P]),
         "qrk_handshake_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, SZ, P, P, P, P, P, P, P]),
         "qrk_base64_encode_batch": (ct.c_int, [P, SZ, P, SZ, P, P]),

@@ -257,3 +257,18 @@ class BatchKEM:
         self._check(LIB.qrk_hqc_supports(self._ctx, self.alg.encode(), kind, r.shape[0], _dptr(r), _dptr(out),
                                           self._stream()), "hqc_supports")
         return out
+
+    def hqc_code_decode(self, sk, ct_):
+        """HQC decoder stages of Decaps alone on device sk [n, sk_len] / ct [n, ct_len]: returns
+        (syms [n, n1], the Reed-Muller symbols decoded from v - u y; mprime [n, k], the message the
+        Reed-Solomon decoder returns for them) (test hook, qrk_hqc_code_decode)."""
+        if not self.alg.startswith("HQC-"):
+            raise ValueError(f"not an HQC parameter set: {self.alg}")
+        n = _check_dev(sk, self.sk_len, "code_decode sk").shape[0]
+        _check_dev(ct_, self.ct_len, "code_decode ct", n)
+        k = self.enc_coins - 16
+        n1 = {16: 46, 24: 56, 32: 90}[k]
+        syms, mp = self._empty(n, n1), self._empty(n, k)
+        self._check(LIB.qrk_hqc_code_decode(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(syms), _dptr(mp),
+                                            self._stream()), "hqc_code_decode")
+        return syms, mp

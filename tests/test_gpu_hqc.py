@@ -4,6 +4,9 @@ Bar: byte-exact pk / sk / ct / ss and identical decaps return codes for every in
 (integer work).  Checker: the C oracle (oracle/src/hqc.c), held to the pure-Python
 restatement and the frozen vectors in tests/test_hqc_oracle.py.  PARITY UNPINNED against
 liboqs itself (no HQC KATs offline).  Sizes are ragged; the chunked path is covered.
+Every accepted ciphertext here is an honest one (the decoder corrects next to nothing);
+tests/test_gpu_hqc_decoder.py holds the RM / Reed-Solomon decoder to the spec at and beyond
+its correction radius.
 """
 import hashlib
 import json
