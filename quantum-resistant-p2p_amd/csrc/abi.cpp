@@ -55,21 +55,38 @@ static AlgInfo ALGS[] = {
 };
 static const int NALG = (int)(sizeof(ALGS) / sizeof(ALGS[0]));
 
-// Names liboqs supports that this engine does not implement (listed so that
-// OQS_KEM_alg_is_enabled answers 0 rather than the name being unknown, the
-// distinction oqs.py:265-269 draws between MechanismNotEnabledError and
-// MechanismNotSupportedError).  Every KEM the reference selects is implemented.
-static const char* UNIMPLEMENTED[] = {nullptr};
-static const int NUNIMPL = 0;
-
 const AlgInfo* find_alg(const char* name) {
   if (!name) return nullptr;
   for (int i = 0; i < NALG; ++i)
     if (!strcmp(ALGS[i].name, name)) return &ALGS[i];
   return nullptr;
 }
-int alg_count() { return NALG; }
-const AlgInfo* alg_at(int i) { return (i >= 0 && i < NALG) ? &ALGS[i] : nullptr; }
+
+// Everything the driver needs to know about a family, indexed by Family.  A launcher whose
+// `sets_status` flag is false never touches `status`: run_batch zeroes it before the launch.
+struct FamilyOps {
+  size_t (*scratch_bytes)(const AlgInfo&, size_t chunk);
+  hipError_t (*cleanse)(const AlgInfo&, size_t n, void* scratch, hipStream_t);
+  hipError_t (*keypair)(const AlgInfo&, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
+                        const Streams&);
+  hipError_t (*encaps)(const AlgInfo&, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* coins,
+                       int32_t* status, void* scratch, const Streams&);
+  hipError_t (*decaps)(const AlgInfo&, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t* status,
+                       void* scratch, const Streams&);
+  bool encaps_sets_status, decaps_sets_status;  // the kernels write every status word themselves
+  const char* alg_version;
+};
+static const FamilyOps FAMILIES[] = {
+    // ML-KEM decapsulation rejects implicitly; FrodoKEM and HQC encapsulation have no public-key check
+    {mlkem_scratch_bytes, mlkem_cleanse, mlkem_keypair, mlkem_encaps, mlkem_decaps, true, false,
+     "FIPS203 (qrkem gfx950)"},
+    {frodo_scratch_bytes, frodo_cleanse, frodo_keypair, frodo_encaps, frodo_decaps, false, false,
+     "FrodoKEM round 3 (qrkem gfx950)"},
+    {hqc_scratch_bytes, hqc_cleanse, hqc_keypair, hqc_encaps, hqc_decaps, false, true,
+     "HQC 2023-04-30 (qrkem gfx950)"},
+};
+static_assert((int)Family::MLKEM == 0 && (int)Family::FRODO == 1 && (int)Family::HQC == 2, "FAMILIES order");
+static const FamilyOps& ops_of(const AlgInfo& a) { return FAMILIES[(int)a.family]; }
 
 }  // namespace qrk
 
@@ -158,15 +175,10 @@ struct qrk_ctx {
   uint32_t* kg_cnt = nullptr;     // multi-workgroup ML-KEM KeyGen arrival counters (zeroed at allocation)
   bool kg_dirty = false;          // a pipelined KeyGen failed: a straggler may have set a flag word
                                   // after the collector's reset, or stored scratch after its wipe
-  bool kg_err_next = false;       // run_batch: hand the KeyGen error word (hflag[1]) to the next launch
-  uint64_t* xof_keep_next = nullptr;        // run_batch: Streams::xof_keep / xof_given of the next
-  const uint64_t* xof_given_next = nullptr;  // call (handshake driver, one chunk)
   uint32_t* fixc = nullptr;       // ML-KEM SampleNTT fix-up counters of chunks <= 2^15 (Streams::fixc)
   int fixp = 0;                   // the counter the next such chunk counts into
   bool fixc_dirty = false;        // a chunk's launches failed after the parity flip: re-zero both
-  uint32_t ticket = 0;
-  bool flag_next = false;         // run_batch: hand the flag to the next launch
-  const uint8_t* hin_next = nullptr;  // ... and the public input's host copy (a by-value kernel argument)
+  uint32_t ticket = 0;            // what the last single-shot call asked its kernel to store in hflag[0]
   hipStream_t io_stream = nullptr;
   int streams = 0;            // 0: multi-role launches, 1: serial (one kernel per launch)
   hipEvent_t ev_last = nullptr;  // recorded at the end of the last call that used the scratch
@@ -269,41 +281,39 @@ static int os_random(uint8_t* out, size_t n) {
   return 0;
 }
 
-static size_t scratch_for(const AlgInfo& a, size_t chunk) {
-  switch (a.family) {
-    case Family::MLKEM: return mlkem_scratch_bytes(a, chunk);
-    case Family::FRODO: return frodo_scratch_bytes(a, chunk);
-    default: return hqc_scratch_bytes(a, chunk);
-  }
-}
-
-static hipError_t cleanse_records(const AlgInfo& a, size_t n, void* scratch, hipStream_t st) {
-  switch (a.family) {
-    case Family::MLKEM: return mlkem_cleanse(a, n, scratch, st);
-    case Family::FRODO: return frodo_cleanse(a, n, scratch, st);
-    default: return hqc_cleanse(a, n, scratch, st);
-  }
-}
-
 static const AlgInfo* resolve(const char* alg) {
   const AlgInfo* a = find_alg(alg);
-  if (!a) {
-    for (int i = 0; alg && i < NUNIMPL; ++i)
-      if (!strcmp(UNIMPLEMENTED[i], alg)) {
-        fail(std::string("KEM not enabled in this build: ") + alg);
-        return nullptr;
-      }
-    fail(std::string("unsupported KEM: ") + (alg ? alg : "(null)"));
-    return nullptr;
-  }
-  if (!a->enabled) {
-    fail(std::string("KEM not enabled in this build: ") + alg);
-    return nullptr;
-  }
-  return a;
+  if (a && a->enabled) return a;
+  fail(std::string(a ? "KEM not enabled in this build: " : "unsupported KEM: ") + (alg ? alg : "(null)"));
+  return nullptr;
 }
 
+// The opening of an ABI call on a context: null check, algorithm, context lock ...
+#define QRK_RESOLVE(ctx, alg)                \
+  if (!(ctx)) return fail("null context");   \
+  const AlgInfo* a = resolve(alg);           \
+  if (!a) return -1;                         \
+  std::lock_guard<std::mutex> lk((ctx)->mu);
+// ... and of a hook that reads a context's buffers back: null checks, context lock, its device
+// current, the previous call's device work complete
+#define QRK_INSPECT(ctx, args_ok)                           \
+  if (!(ctx) || !(args_ok)) return fail("null argument");   \
+  std::lock_guard<std::mutex> lk((ctx)->mu);                \
+  DeviceGuard device_guard;                                 \
+  if (device_guard.set((ctx)->device)) return -1;           \
+  ctx_quiesce(ctx);
+
 enum class Op { KEYPAIR, ENCAPS, DECAPS };
+
+// What one caller asks of one run_batch call beyond the batch itself.  Each option takes effect
+// only where run_batch says so; the public device-pointer entry points pass none.
+struct CallOpts {
+  bool flag = false;                  // single-shot: the kernel stores ctx->ticket in the completion flag ...
+  const uint8_t* host_in1 = nullptr;  // ... and may take the public input's host copy as a by-value argument
+  bool kg_err = false;                // ML-KEM KeyGen: hand the launch the error word, hflag[1]
+  uint64_t* xof_keep = nullptr;       // Streams::xof_keep (KeyGen) / xof_given (Decaps): the handshake
+  const uint64_t* xof_given = nullptr;  // driver's A_hat hand-over
+};
 
 // FrodoKEM scratch is 0.14-0.53 MB per handshake, HQC's 9-24 KB: their chunks are capped so
 // scratch stays near QRK_SCRATCH_GIB (48 GiB of the 288 GB HBM by default: a 2^16 FrodoKEM batch in
@@ -314,7 +324,7 @@ enum class Op { KEYPAIR, ENCAPS, DECAPS };
 static size_t chunk_for(const qrk_ctx* ctx, const AlgInfo& a) {
   size_t cap = ctx->chunk;
   if (a.family != Family::MLKEM) {
-    const size_t per_hs = scratch_for(a, 1024) / 1024 + 1;
+    const size_t per_hs = ops_of(a).scratch_bytes(a, 1024) / 1024 + 1;
     cap = std::min(cap, std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_hs / 64 * 64));
   }
   return cap;
@@ -339,10 +349,20 @@ struct CoinWipe {
   }
 };
 
+// Queues, on `st`, the re-zero of what a failed pipelined ML-KEM KeyGen may have left behind
+// (qrk_ctx::kg_dirty): its flag words and the head of the scratch its workgroups store to.
+static hipError_t kg_rezero(qrk_ctx* ctx, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(ctx->kg_cnt, 0, mlkem_kg_flag_words() * sizeof(uint32_t), st);
+  if (e == hipSuccess && ctx->scratch)
+    e = hipMemsetAsync(ctx->scratch, 0, std::min(ctx->scratch_bytes, mlkem_kg_scratch_bytes()), st);
+  return e;
+}
+
 // Core batched driver over device pointers, chunked.
 static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o1, uint8_t* o2, const uint8_t* i1,
-                     const uint8_t* i2, int32_t* status, hipStream_t st) {
+                     const uint8_t* i2, int32_t* status, hipStream_t st, const CallOpts& opts) {
   if (n == 0) return 0;
+  const FamilyOps& f = ops_of(a);
   DeviceGuard device_guard;
   if (device_guard.set(ctx->device)) return -1;
   if (ctx_order(ctx, st)) return -1;
@@ -351,7 +371,7 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
   const size_t cap = chunk_for(ctx, a);
   const size_t nchunks = (n + cap - 1) / cap;
   const size_t chunk = std::min(cap, ((n + nchunks - 1) / nchunks + 63) & ~(size_t)63);
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_for(a, chunk), st)) return -1;
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, f.scratch_bytes(a, chunk), st)) return -1;
   // coins: NULL -> OS CSPRNG, uploaded to device staging
   const uint8_t* coins = (op == Op::KEYPAIR) ? i1 : (op == Op::ENCAPS ? i2 : nullptr);
   const size_t clen = (op == Op::KEYPAIR) ? a.kp_coins : a.enc_coins;
@@ -383,10 +403,10 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
   // streams == 1: the documented serial schedule (one kernel per launch: per-kernel timings in
   // isolation, qrkem.h); otherwise independent kernels of one operation share launches
   S.serial = ctx->streams == 1;
-  if (ctx->flag_next) {
+  if (opts.flag) {
     S.done = ctx->hflag_dev;
     S.ticket = ctx->ticket;
-    S.host_in1 = ctx->hin_next;
+    S.host_in1 = opts.host_in1;
   }
   if (a.family == Family::MLKEM && op == Op::KEYPAIR && n <= mlkem_kg_multi_max()) {
     if (!ctx->kg_cnt) {
@@ -395,18 +415,16 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
       if (e != hipSuccess) return hip_fail("hipMalloc(kg_cnt)", e);
     }
     if (ctx->kg_dirty) {  // stream-ordered behind the failed call's kernel
-      hipError_t e = hipMemsetAsync(ctx->kg_cnt, 0, mlkem_kg_flag_words() * sizeof(uint32_t), st);
-      if (e == hipSuccess && ctx->scratch)
-        e = hipMemsetAsync(ctx->scratch, 0, std::min(ctx->scratch_bytes, mlkem_kg_scratch_bytes()), st);
+      const hipError_t e = kg_rezero(ctx, st);
       if (e != hipSuccess) return hip_fail("hipMemsetAsync(kg_cnt)", e);
       ctx->kg_dirty = false;
     }
     S.kg_cnt = ctx->kg_cnt;
-    if (ctx->kg_err_next) S.kg_err = ctx->hflag_dev + 1;
+    if (opts.kg_err) S.kg_err = ctx->hflag_dev + 1;
   }
   if (a.family == Family::MLKEM && n <= chunk && n > mlkem_small_max()) {
-    S.xof_keep = op == Op::KEYPAIR ? ctx->xof_keep_next : nullptr;
-    S.xof_given = op == Op::DECAPS ? ctx->xof_given_next : nullptr;
+    S.xof_keep = op == Op::KEYPAIR ? opts.xof_keep : nullptr;
+    S.xof_given = op == Op::DECAPS ? opts.xof_given : nullptr;
   }
   if (a.family == Family::MLKEM && op != Op::KEYPAIR) {
     if (!ctx->fixc) {
@@ -429,56 +447,21 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     hipError_t e = hipSuccess;
     g_launch_err = hipSuccess;
     (void)hipGetLastError();  // clear a stale error state (e.g. a caller's hipErrorNotReady query)
-    if (a.family == Family::MLKEM) {
-      switch (op) {
-        case Op::KEYPAIR:
-          e = mlkem_keypair(a, m, o1 + off * a.pk, o2 + off * a.sk, coins + off * clen, ctx->scratch, S);
-          break;
-        case Op::ENCAPS:
-          e = mlkem_encaps(a, m, o1 + off * a.ct, o2 + off * a.ss, i1 + off * a.pk, coins + off * clen,
-                           status ? status + off : nullptr, ctx->scratch, S);
-          break;
-        case Op::DECAPS:
-          if (status) e = hipMemsetAsync(status + off, 0, m * sizeof(int32_t), st);
-          if (e == hipSuccess)
-            e = mlkem_decaps(a, m, o1 + off * a.ss, i1 + off * a.ct, i2 + off * a.sk, ctx->scratch, S);
-          break;
-      }
-    } else if (a.family == Family::HQC) {
-      switch (op) {
-        case Op::KEYPAIR:
-          e = hqc_keypair(a, m, o1 + off * a.pk, o2 + off * a.sk, coins + off * clen, ctx->scratch, S);
-          break;
-        case Op::ENCAPS:
-          // HQC encapsulation has no public-key validity check: status is always 0
-          if (status) e = hipMemsetAsync(status + off, 0, m * sizeof(int32_t), st);
-          if (e == hipSuccess)
-            e = hqc_encaps(a, m, o1 + off * a.ct, o2 + off * a.ss, i1 + off * a.pk, coins + off * clen, ctx->scratch,
-                           S);
-          break;
-        case Op::DECAPS:
-          e = hqc_decaps(a, m, o1 + off * a.ss, i1 + off * a.ct, i2 + off * a.sk, status ? status + off : nullptr,
-                         ctx->scratch, S);
-          break;
-      }
-    } else {
-      switch (op) {
-        case Op::KEYPAIR:
-          e = frodo_keypair(a, m, o1 + off * a.pk, o2 + off * a.sk, coins + off * clen, ctx->scratch, S);
-          break;
-        case Op::ENCAPS:
-          // FrodoKEM encapsulation has no public-key validity check: status is always 0
-          if (status) e = hipMemsetAsync(status + off, 0, m * sizeof(int32_t), st);
-          if (e == hipSuccess)
-            e = frodo_encaps(a, m, o1 + off * a.ct, o2 + off * a.ss, i1 + off * a.pk, coins + off * clen,
-                             ctx->scratch, S);
-          break;
-        case Op::DECAPS:
-          if (status) e = hipMemsetAsync(status + off, 0, m * sizeof(int32_t), st);
-          if (e == hipSuccess)
-            e = frodo_decaps(a, m, o1 + off * a.ss, i1 + off * a.ct, i2 + off * a.sk, ctx->scratch, S);
-          break;
-      }
+    int32_t* const stat = status ? status + off : nullptr;
+    switch (op) {
+      case Op::KEYPAIR:
+        e = f.keypair(a, m, o1 + off * a.pk, o2 + off * a.sk, coins + off * clen, ctx->scratch, S);
+        break;
+      case Op::ENCAPS:
+        if (stat && !f.encaps_sets_status) e = hipMemsetAsync(stat, 0, m * sizeof(int32_t), st);
+        if (e == hipSuccess)
+          e = f.encaps(a, m, o1 + off * a.ct, o2 + off * a.ss, i1 + off * a.pk, coins + off * clen, stat, ctx->scratch,
+                       S);
+        break;
+      case Op::DECAPS:
+        if (stat && !f.decaps_sets_status) e = hipMemsetAsync(stat, 0, m * sizeof(int32_t), st);
+        if (e == hipSuccess) e = f.decaps(a, m, o1 + off * a.ss, i1 + off * a.ct, i2 + off * a.sk, stat, ctx->scratch, S);
+        break;
     }
     HT(4);
     if (e == hipSuccess) e = g_launch_err;
@@ -487,7 +470,7 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
       return hip_fail("kernel launch", e);
     }
     // key material of this chunk (seeds, m', K', Kbar, ...) does not outlive the call
-    e = cleanse_records(a, m, ctx->scratch, st);
+    e = f.cleanse(a, m, ctx->scratch, st);
     if (e != hipSuccess) return hip_fail("hipMemsetAsync(cleanse)", e);
   }
   return 0;
@@ -506,18 +489,36 @@ static int flag_ready(qrk_ctx* ctx) {
   return 0;
 }
 
-// Zero-copy host call (see run_batch_host): inputs | outputs packed in the pinned mirror, which
-// the kernel addresses through its device mapping.
-static int run_small_host(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o1, uint8_t* o2,
-                          const uint8_t* i1, const uint8_t* i2, int32_t* status, size_t l_o1, size_t l_o2,
-                          size_t l_i1, size_t l_i2, hipStream_t st) {
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t b_i1 = al(n * l_i1), b_i2 = al(n * l_i2), b_o1 = al(n * l_o1), b_o2 = al(n * l_o2);
-  const size_t b_st = al(n * sizeof(int32_t)), total = b_i1 + b_i2 + b_o1 + b_o2 + b_st;
-  if (ctx->hio_bytes < total) {
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Packed I/O of a host-pointer call of n handshakes: the inputs (i1 | i2, one H2D copy), then the
+// outputs (o1 | o2 | status, one D2H copy), every slot rounded up to 256 bytes.  l_*: bytes per
+// handshake (0: no such buffer); o_*: byte offset of the slot (i1 is at 0, the outputs at o_o1).
+struct IoLayout {
+  size_t n, l_i1, l_i2, l_o1, l_o2, l_st;
+  size_t o_i2, o_o1, o_o2, o_st, total;
+  IoLayout(const AlgInfo& a, Op op, size_t n_, bool coins, bool status) : n(n_) {
+    switch (op) {
+      case Op::KEYPAIR: l_i1 = coins ? a.kp_coins : 0, l_i2 = 0, l_o1 = a.pk, l_o2 = a.sk; break;
+      case Op::ENCAPS: l_i1 = a.pk, l_i2 = coins ? a.enc_coins : 0, l_o1 = a.ct, l_o2 = a.ss; break;
+      default: l_i1 = a.ct, l_i2 = a.sk, l_o1 = a.ss, l_o2 = 0; break;
+    }
+    l_st = status ? sizeof(int32_t) : 0;
+    o_i2 = al256(n * l_i1), o_o1 = o_i2 + al256(n * l_i2), o_o2 = o_o1 + al256(n * l_o1);
+    o_st = o_o2 + al256(n * l_o2), total = o_st + al256(n * l_st);
+  }
+};
+
+// Zero-copy host call (see run_batch_host): the layout L (coins and status slots always present)
+// lives in the pinned mirror, which the kernel addresses through its device mapping.
+static int run_small_host(qrk_ctx* ctx, const AlgInfo& a, Op op, const IoLayout& L, uint8_t* o1, uint8_t* o2,
+                          const uint8_t* i1, const uint8_t* i2, int32_t* status) {
+  const size_t n = L.n;
+  hipStream_t st = ctx->io_stream;
+  if (ctx->hio_bytes < L.total) {
     ctx_quiesce(ctx);
     if (ctx->hio) OQS_MEM_cleanse(ctx->hio, ctx->hio_bytes);
-    if (grow_pinned(&ctx->hio, &ctx->hio_bytes, total)) return -1;
+    if (grow_pinned(&ctx->hio, &ctx->hio_bytes, L.total)) return -1;
     ctx->hio_dev = nullptr;
   }
   if (!ctx->hio_dev) {
@@ -527,43 +528,37 @@ static int run_small_host(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8
     ctx->hio_dev = (uint8_t*)d;
   }
   uint8_t* h = ctx->hio;
-  const size_t o_i2 = b_i1, o_o1 = b_i1 + b_i2, o_o2 = o_o1 + b_o1, o_st = o_o2 + b_o2;
   // inputs (coins the caller did not supply come from the OS CSPRNG)
-  if (l_i1) {
-    if (i1) memcpy(h, i1, n * l_i1);
-    else if (os_random(h, n * l_i1)) return -1;
+  if (L.l_i1) {
+    if (i1) memcpy(h, i1, n * L.l_i1);
+    else if (os_random(h, n * L.l_i1)) return -1;
   }
-  if (l_i2) {
-    if (i2) memcpy(h + o_i2, i2, n * l_i2);
-    else if (os_random(h + o_i2, n * l_i2)) return -1;
+  if (L.l_i2) {
+    if (i2) memcpy(h + L.o_i2, i2, n * L.l_i2);
+    else if (os_random(h + L.o_i2, n * L.l_i2)) return -1;
   }
-  memset(h + o_st, 0, n * sizeof(int32_t));
+  memset(h + L.o_st, 0, n * L.l_st);
   HT(2);
   uint8_t* d = ctx->hio_dev;
+  CallOpts opts;
   // n == 1: the kernel stores a ticket in fine-grained pinned memory once its outputs are visible,
   // and the host spins on it (about 4 us sooner than hipStreamSynchronize wakes up)
-  const bool spin = n == 1 && flag_ready(ctx) == 0;
+  opts.flag = n == 1 && flag_ready(ctx) == 0;
   // ML-KEM KeyGen: the pipelined kernel's error word, hflag[1] (the flag's 64-byte line)
-  const bool kg_err = op == Op::KEYPAIR && n <= mlkem_kg_multi_max() && flag_ready(ctx) == 0;
-  if (kg_err) {
-    __atomic_store_n(ctx->hflag + 1, 0u, __ATOMIC_RELEASE);
-    ctx->kg_err_next = true;
-  }
-  if (spin) {
+  opts.kg_err = op == Op::KEYPAIR && n <= mlkem_kg_multi_max() && flag_ready(ctx) == 0;
+  if (opts.kg_err) __atomic_store_n(ctx->hflag + 1, 0u, __ATOMIC_RELEASE);
+  if (opts.flag) {
     ctx->ticket = ctx->ticket + 1 ? ctx->ticket + 1 : 1;
-    ctx->flag_next = true;
     // the public input (Encaps pk, Decaps c) may travel as a kernel argument; KeyGen's coins never
-    ctx->hin_next = (op != Op::KEYPAIR && l_i1) ? h : nullptr;
+    opts.host_in1 = (op != Op::KEYPAIR && L.l_i1) ? h : nullptr;
   }
   // ML-KEM decapsulation reports no status (implicit rejection): only encapsulation writes it
-  int rc = run_batch(ctx, a, op, n, d + o_o1, l_o2 ? d + o_o2 : nullptr, l_i1 ? d : nullptr, l_i2 ? d + o_i2 : nullptr,
-                     (status && op == Op::ENCAPS) ? (int32_t*)(d + o_st) : nullptr, st);
+  int rc = run_batch(ctx, a, op, n, d + L.o_o1, L.l_o2 ? d + L.o_o2 : nullptr, L.l_i1 ? d : nullptr,
+                     L.l_i2 ? d + L.o_i2 : nullptr, (status && op == Op::ENCAPS) ? (int32_t*)(d + L.o_st) : nullptr, st,
+                     opts);
   HT(5);
-  ctx->flag_next = false;
-  ctx->hin_next = nullptr;
-  ctx->kg_err_next = false;
   hipError_t e = hipSuccess;
-  if (!rc && spin) {
+  if (!rc && opts.flag) {
     // bounded spin; a kernel that never stores the ticket (a launch or execution error) falls
     // back to the stream synchronise, which reports it
     const auto t0 = std::chrono::steady_clock::now();
@@ -583,25 +578,23 @@ static int run_small_host(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8
   if (!rc && e != hipSuccess) rc = hip_fail("kernel execution", e);
   // the collector stores the error word before the ticket (or the kernel's end, which the stream
   // synchronise waited for)
-  if (!rc && kg_err && __atomic_load_n(ctx->hflag + 1, __ATOMIC_ACQUIRE) != 0)
+  if (!rc && opts.kg_err && __atomic_load_n(ctx->hflag + 1, __ATOMIC_ACQUIRE) != 0)
     rc = fail("ML-KEM KeyGen: keygen hand-off timeout (a bounded cross-workgroup wait expired)");
-  if (rc && kg_err) ctx->kg_dirty = true;  // re-zeroed (flags, scratch) before the next KeyGen launch
+  if (rc && opts.kg_err) ctx->kg_dirty = true;  // re-zeroed (flags, scratch) before the next KeyGen launch
   if (!rc) {
-    memcpy(o1, h + o_o1, n * l_o1);
-    if (l_o2) memcpy(o2, h + o_o2, n * l_o2);
-    if (status) memcpy(status, h + o_st, n * sizeof(int32_t));
+    memcpy(o1, h + L.o_o1, n * L.l_o1);
+    if (L.l_o2) memcpy(o2, h + L.o_o2, n * L.l_o2);
+    if (status) memcpy(status, h + L.o_st, n * L.l_st);
   }
   if (rc) (void)hipStreamSynchronize(st);  // nothing may still read or write the mirror
   if (rc && ctx->kg_dirty && ctx->kg_cnt) {
     // wipe the secret scratch a straggler may have written after the collector's wipe now, not at
     // the next KeyGen (run_batch re-zeroes again if this fails)
-    hipError_t w = hipMemsetAsync(ctx->kg_cnt, 0, mlkem_kg_flag_words() * sizeof(uint32_t), st);
-    if (w == hipSuccess && ctx->scratch)
-      w = hipMemsetAsync(ctx->scratch, 0, std::min(ctx->scratch_bytes, mlkem_kg_scratch_bytes()), st);
+    hipError_t w = kg_rezero(ctx, st);
     if (w == hipSuccess) w = hipStreamSynchronize(st);
     if (w == hipSuccess) ctx->kg_dirty = false;
   }
-  OQS_MEM_cleanse(h, total);  // coins, secret keys and shared secrets do not outlive the call
+  OQS_MEM_cleanse(h, L.total);  // coins, secret keys and shared secrets do not outlive the call
   HT(7);
   return rc;
 }
@@ -619,58 +612,43 @@ static int run_batch_host(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8
   // zero-copy: the kernel reads its inputs from and writes its outputs to the pinned mirror, and
   // coins are drawn straight into it, so a call is one launch and one synchronise.
   const bool zc = a.family == Family::MLKEM && n <= mlkem_small_max();
-  size_t l_o1, l_o2, l_i1, l_i2;
-  switch (op) {
-    case Op::KEYPAIR: l_o1 = a.pk, l_o2 = a.sk, l_i1 = (i1 || zc) ? a.kp_coins : 0, l_i2 = 0; break;
-    case Op::ENCAPS: l_o1 = a.ct, l_o2 = a.ss, l_i1 = a.pk, l_i2 = (i2 || zc) ? a.enc_coins : 0; break;
-    default: l_o1 = a.ss, l_o2 = 0, l_i1 = a.ct, l_i2 = a.sk; break;
-  }
-  const size_t l_st = status ? sizeof(int32_t) : 0;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // inputs first (one H2D), then outputs (one D2H)
-  const size_t b_i1 = al(n * l_i1), b_i2 = al(n * l_i2), b_o1 = al(n * l_o1), b_o2 = al(n * l_o2),
-               b_st = al(n * l_st);
-  const size_t in_bytes = b_i1 + b_i2, out_bytes = b_o1 + b_o2 + b_st;
+  // coins the caller left out get no slot here (run_batch draws them); zero-copy calls reserve
+  // the coin and status slots unconditionally
+  const IoLayout L(a, op, n, zc || (op == Op::KEYPAIR ? i1 : i2), zc || status);
   if (!ctx->io_stream) {
     hipError_t e = hipStreamCreateWithFlags(&ctx->io_stream, hipStreamNonBlocking);
     if (e != hipSuccess) return hip_fail("hipStreamCreate(io)", e);
   }
   hipStream_t st = ctx->io_stream;
-  if (zc) return run_small_host(ctx, a, op, n, o1, o2, i1, i2, status, l_o1, l_o2, l_i1, l_i2, st);
-  if (grow_device(ctx, (void**)&ctx->dio, &ctx->dio_bytes, in_bytes + out_bytes, st)) return -1;
-  if (ctx->hio_bytes < in_bytes + out_bytes) ctx->hio_dev = nullptr;  // reallocated below
-  if (grow_pinned(&ctx->hio, &ctx->hio_bytes, in_bytes + out_bytes)) return -1;
-  uint8_t *d_i1 = ctx->dio, *d_i2 = d_i1 + b_i1, *d_o1 = d_i2 + b_i2, *d_o2 = d_o1 + b_o1, *d_st = d_o2 + b_o2;
-  uint8_t* h = ctx->hio;
-  if (l_i1) memcpy(h, i1, n * l_i1);
-  if (l_i2) memcpy(h + b_i1, i2, n * l_i2);
-  hipError_t e = in_bytes ? hipMemcpyAsync(ctx->dio, h, in_bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  if (zc) return run_small_host(ctx, a, op, L, o1, o2, i1, i2, status);
+  if (grow_device(ctx, (void**)&ctx->dio, &ctx->dio_bytes, L.total, st)) return -1;
+  if (ctx->hio_bytes < L.total) ctx->hio_dev = nullptr;  // reallocated below
+  if (grow_pinned(&ctx->hio, &ctx->hio_bytes, L.total)) return -1;
+  uint8_t *d = ctx->dio, *h = ctx->hio;
+  if (L.l_i1) memcpy(h, i1, n * L.l_i1);
+  if (L.l_i2) memcpy(h + L.o_i2, i2, n * L.l_i2);
+  hipError_t e = L.o_o1 ? hipMemcpyAsync(d, h, L.o_o1, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e != hipSuccess) return hip_fail("hipMemcpyAsync(H2D)", e);
-  int rc = run_batch(ctx, a, op, n, d_o1, l_o2 ? d_o2 : nullptr, l_i1 ? d_i1 : nullptr, l_i2 ? d_i2 : nullptr,
-                     status ? (int32_t*)d_st : nullptr, st);
+  int rc = run_batch(ctx, a, op, n, d + L.o_o1, L.l_o2 ? d + L.o_o2 : nullptr, L.l_i1 ? d : nullptr,
+                     L.l_i2 ? d + L.o_i2 : nullptr, status ? (int32_t*)(d + L.o_st) : nullptr, st, {});
   if (rc) return rc;
-  uint8_t* ho = h + in_bytes;
-  e = hipMemcpyAsync(ho, d_o1, out_bytes, hipMemcpyDeviceToHost, st);
+  e = hipMemcpyAsync(h + L.o_o1, d + L.o_o1, L.total - L.o_o1, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return hip_fail("kernel execution / D2H", e);
-  memcpy(o1, ho, n * l_o1);
-  if (l_o2) memcpy(o2, ho + b_o1, n * l_o2);
-  if (status) memcpy(status, ho + b_o1 + b_o2, n * l_st);
-  // the staged copies of secret keys, coins and shared secrets do not outlive the call:
-  // KeyGen (coins in, sk out), Encaps (coins in, ss out), Decaps (sk in, ss out)
+  memcpy(o1, h + L.o_o1, n * L.l_o1);
+  if (L.l_o2) memcpy(o2, h + L.o_o2, n * L.l_o2);
+  if (status) memcpy(status, h + L.o_st, n * L.l_st);
+  // the staged copies of secrets do not outlive the call: coins (KeyGen's i1, Encaps' i2) or sk
+  // (Decaps' i2) in, sk or ss (o2; Decaps' o1) out
   struct Span {
     size_t off, len;
   };
-  const Span sec[2] = {op == Op::KEYPAIR   ? Span{0, n * l_i1}
-                       : op == Op::ENCAPS  ? Span{b_i1, n * l_i2}
-                                           : Span{b_i1, n * l_i2},
-                       op == Op::KEYPAIR ? Span{in_bytes + b_o1, n * l_o2}
-                       : op == Op::ENCAPS ? Span{in_bytes + b_o1, n * l_o2}
-                                          : Span{in_bytes, n * l_o1}};
+  const Span sec[2] = {op == Op::KEYPAIR ? Span{0, n * L.l_i1} : Span{L.o_i2, n * L.l_i2},
+                       op == Op::DECAPS ? Span{L.o_o1, n * L.l_o1} : Span{L.o_o2, n * L.l_o2}};
   for (const Span& z : sec) {
     if (!z.len) continue;
     OQS_MEM_cleanse(h + z.off, z.len);
-    (void)hipMemsetAsync(ctx->dio + z.off, 0, z.len, st);
+    (void)hipMemsetAsync(d + z.off, 0, z.len, st);
   }
   return 0;
 }
@@ -740,13 +718,9 @@ void OQS_init(void) {}
 
 const char* OQS_version(void) { return "0.12.0-qrkem-gfx950"; }
 
-size_t OQS_KEM_alg_count(void) { return (size_t)(NALG + NUNIMPL); }
+size_t OQS_KEM_alg_count(void) { return (size_t)NALG; }
 
-const char* OQS_KEM_alg_identifier(size_t i) {
-  if (i < (size_t)NALG) return ALGS[i].name;
-  if (i < (size_t)(NALG + NUNIMPL)) return UNIMPLEMENTED[i - NALG];
-  return nullptr;
-}
+const char* OQS_KEM_alg_identifier(size_t i) { return i < (size_t)NALG ? ALGS[i].name : nullptr; }
 
 int OQS_KEM_alg_is_enabled(const char* method_name) {
   const AlgInfo* a = find_alg(method_name);
@@ -759,9 +733,7 @@ OQS_KEM* OQS_KEM_new(const char* method_name) {
   OQS_KEM* k = (OQS_KEM*)calloc(1, sizeof(OQS_KEM));
   if (!k) return nullptr;
   k->method_name = a->name;
-  k->alg_version = a->family == Family::MLKEM   ? "FIPS203 (qrkem gfx950)"
-                   : a->family == Family::FRODO ? "FrodoKEM round 3 (qrkem gfx950)"
-                                                : "HQC 2023-04-30 (qrkem gfx950)";
+  k->alg_version = ops_of(*a).alg_version;
   k->claimed_nist_level = (uint8_t)a->level;
   k->ind_cca = true;
   k->length_public_key = a->pk;
@@ -901,11 +873,7 @@ int qrk_ctx_set_chunk(qrk_ctx* ctx, size_t chunk) {
 size_t qrk_ctx_scratch_bytes(const qrk_ctx* ctx) { return ctx ? ctx->scratch_bytes : 0; }
 
 int qrk_ctx_staging_residue(qrk_ctx* ctx, uint64_t out[3]) {
-  if (!ctx || !out) return fail("null argument");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  ctx_quiesce(ctx);
+  QRK_INSPECT(ctx, out);
   out[0] = out[1] = out[2] = 0;
   for (size_t i = 0; i < ctx->hstage_bytes; ++i) out[0] += ctx->hstage[i] != 0;
   const void* src[2] = {ctx->dstage, ctx->scratch};
@@ -927,7 +895,7 @@ int qrk_ctx_staging_residue(qrk_ctx* ctx, uint64_t out[3]) {
 // (PRF item N = role < 2K, row r = role - 2K + 1) publishes its payload and flags 150 ms late, past
 // every bounded wait (-1: off).  Process-wide.
 extern "C" int qrk_dbg_kg_late(int role) {
-  g_kg_dbg_late = role;
+  g_kg_dbg_late.store(role, std::memory_order_relaxed);
   return 0;
 }
 
@@ -935,15 +903,11 @@ extern "C" int qrk_dbg_kg_late(int role) {
 // right after the SampleNTT fix-up counter parity flip, before their first launch (0: off), and the
 // context's two fix-up counter words and its parity read back (the re-zero path).
 extern "C" int qrk_dbg_fail_after_flip(int on) {
-  g_dbg_fail_after_flip = on;
+  g_dbg_fail_after_flip.store(on, std::memory_order_relaxed);
   return 0;
 }
 extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
-  if (!ctx || !out || !parity) return fail("null argument");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  ctx_quiesce(ctx);
+  QRK_INSPECT(ctx, out && parity);
   out[0] = out[1] = 0;
   *parity = ctx->fixp;
   if (!ctx->fixc) return 0;
@@ -954,11 +918,7 @@ extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
 // Tests only (not in qrkem.h): nonzero words among the context's single-shot KeyGen flag / counter
 // words, which must be zero between calls (after a failed pipelined KeyGen too).
 extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
-  if (!ctx || !out) return fail("null argument");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  ctx_quiesce(ctx);
+  QRK_INSPECT(ctx, out);
   *out = 0;
   if (!ctx->kg_cnt) return 0;
   std::vector<uint32_t> tmp(mlkem_kg_flag_words());
@@ -970,13 +930,9 @@ extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
 // Tests only (not in qrkem.h): nonzero bytes left in the ML-KEM per-handshake records of a chunk
 // of n handshakes (mlkem_cleanse wipes them after every chunk).
 extern "C" int qrk_dbg_mlkem_records_residue(qrk_ctx* ctx, const char* alg, size_t n, uint64_t* out) {
-  if (!ctx || !out) return fail("null argument");
+  QRK_INSPECT(ctx, out);
   const AlgInfo* a = find_alg(alg);
   if (!a || a->family != Family::MLKEM) return fail("not an ML-KEM algorithm");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  ctx_quiesce(ctx);
   size_t off = 0, bytes = 0;
   mlkem_records_span(*a, (std::min(n, chunk_for(ctx, *a)) + 63) & ~(size_t)63, &off, &bytes);
   if (off + bytes > ctx->scratch_bytes) return fail("the context's scratch does not cover that chunk");
@@ -1041,31 +997,25 @@ int qrk_kem_sizes(const char* alg, size_t out[6]) {
   return 0;
 }
 
-#define QRK_RESOLVE(ctx, alg)                \
-  if (!(ctx)) return fail("null context");   \
-  const AlgInfo* a = resolve(alg);           \
-  if (!a) return -1;                         \
-  std::lock_guard<std::mutex> lk((ctx)->mu);
-
 int qrk_kem_keypair_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
                           void* stream) {
   QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr, (hipStream_t)stream);
+  return run_batch(ctx, *a, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr, (hipStream_t)stream, {});
 }
 int qrk_kem_encaps_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk,
                          const uint8_t* coins, int32_t* status, void* stream) {
   QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::ENCAPS, n, ct, ss, pk, coins, status, (hipStream_t)stream);
+  return run_batch(ctx, *a, Op::ENCAPS, n, ct, ss, pk, coins, status, (hipStream_t)stream, {});
 }
 int qrk_kem_decaps_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
                          void* stream) {
   QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, (hipStream_t)stream);
+  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, (hipStream_t)stream, {});
 }
 int qrk_kem_decaps_batch_status(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                 const uint8_t* sk, int32_t* status, void* stream) {
   QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, status, (hipStream_t)stream);
+  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, status, (hipStream_t)stream, {});
 }
 int qrk_kem_keypair_batch_host(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* pk, uint8_t* sk,
                                const uint8_t* coins) {
@@ -1140,14 +1090,14 @@ int qrk_hqc_code_decode(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   if (device_guard.set(ctx->device)) return -1;
   if (ctx_order(ctx, st)) return -1;
   LastUse last_use{ctx, st};
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_for(*a, (n + 63) & ~(size_t)63), st)) return -1;
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, ops_of(*a).scratch_bytes(*a, (n + 63) & ~(size_t)63), st)) return -1;
   TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
   g_launch_err = hipSuccess;
   (void)hipGetLastError();
   hipError_t e = hqc_code_decode(*a, n, sk, ct, syms, mprime, ctx->scratch, st);
   if (e == hipSuccess) e = g_launch_err;
   if (e != hipSuccess) return hip_fail("hqc_code_decode", e);
-  e = cleanse_records(*a, n, ctx->scratch, st);  // the symbols and m' do not outlive the call
+  e = ops_of(*a).cleanse(*a, n, ctx->scratch, st);  // the symbols and m' do not outlive the call
   return e == hipSuccess ? 0 : hip_fail("hipMemsetAsync(cleanse)", e);
 }
 
@@ -1185,20 +1135,15 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   // (the reference keeps them in Python objects: messaging.py:590-600, 809).
   const size_t chunk = chunk_for(ctx, *a);
   const size_t m0 = std::min(chunk, n);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t b_sk = al(m0 * a->sk), b_ss = al(m0 * a->ss);
+  const size_t b_sk = al256(m0 * a->sk), b_ss = al256(m0 * a->ss);
   // ML-KEM batched chunks: the initiator's sampled matrix A_hat, kept from its KeyGen (:590) for its
   // Decaps (:1038) -- the same rho, so Decaps skips K^2 SampleNTT entries (27 of a handshake's ~174
   // ML-KEM-768 permutations).  Public data (a function of rho): outside the wiped range.
   const bool keep_a = a->family == Family::MLKEM && m0 > mlkem_small_max();
-  const size_t b_mat = keep_a ? al(mlkem_matrix_bytes(*a, m0)) : 0;
+  const size_t b_mat = keep_a ? al256(mlkem_matrix_bytes(*a, m0)) : 0;
   if (grow_device(ctx, (void**)&ctx->hs_scratch, &ctx->hs_scratch_bytes, 2 * b_sk + 2 * b_ss + b_mat, st)) return -1;
   uint8_t *sk_i = ctx->hs_scratch, *sk_r = sk_i + b_sk, *ss_i = sk_r + b_sk, *ss_r = ss_i + b_ss;
   uint64_t* mat_i = keep_a ? (uint64_t*)(ss_r + b_ss) : nullptr;
-  struct NextReset {  // the hand-over fields never outlive one run_batch call
-    qrk_ctx* c;
-    ~NextReset() { c->xof_keep_next = nullptr, c->xof_given_next = nullptr; }
-  } next_reset{ctx};
   // wipes the ephemeral sk / ss on every exit path, error returns included (runs before
   // last_use records the end of the call)
   struct Wipe {
@@ -1211,27 +1156,23 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
     const size_t m = std::min(chunk, n - off);
     auto co = [&](const uint8_t* c, size_t len) { return c ? c + off * len : nullptr; };
     // initiate_key_exchange: ephemeral KeyGen (messaging.py:590); A_hat kept for its Decaps
-    const bool keep = keep_a && m > mlkem_small_max();
-    ctx->xof_keep_next = keep ? mat_i : nullptr;
-    const int rc_kg = run_batch(ctx, *a, Op::KEYPAIR, m, pk_i + off * a->pk, sk_i, co(coins_kp_i, a->kp_coins), nullptr,
-                                nullptr, st);
-    ctx->xof_keep_next = nullptr;
-    if (rc_kg) return -1;
+    CallOpts kg_opts, dec_opts;
+    dec_opts.xof_given = kg_opts.xof_keep = (keep_a && m > mlkem_small_max()) ? mat_i : nullptr;
+    if (run_batch(ctx, *a, Op::KEYPAIR, m, pk_i + off * a->pk, sk_i, co(coins_kp_i, a->kp_coins), nullptr, nullptr, st,
+                  kg_opts))
+      return -1;
     // _handle_key_exchange_init: responder KeyGen (:809, pk sent back at :853) + Encaps (:830)
     if (run_batch(ctx, *a, Op::KEYPAIR, m, pk_r + off * a->pk, sk_r, co(coins_kp_r, a->kp_coins), nullptr, nullptr,
-                  st))
+                  st, {}))
       return -1;
     if (run_batch(ctx, *a, Op::ENCAPS, m, ct + off * a->ct, ss_r, pk_i + off * a->pk, co(coins_enc, a->enc_coins),
-                  nullptr, st))
+                  nullptr, st, {}))
       return -1;
     hipError_t e = hkdf_sha256(m, ss_r, a->ss, a->ss, nullptr, 0, info, info_off ? info_off + off : nullptr,
                                info_len, key_len, key_r + off * key_len, key_len, st);  // :845
     if (e != hipSuccess) return hip_fail("hkdf_sha256", e);
     // _handle_key_exchange_response: Decaps (:1038) + HKDF (:1068)
-    ctx->xof_given_next = keep ? mat_i : nullptr;
-    const int rc_dec = run_batch(ctx, *a, Op::DECAPS, m, ss_i, nullptr, ct + off * a->ct, sk_i, nullptr, st);
-    ctx->xof_given_next = nullptr;
-    if (rc_dec) return -1;
+    if (run_batch(ctx, *a, Op::DECAPS, m, ss_i, nullptr, ct + off * a->ct, sk_i, nullptr, st, dec_opts)) return -1;
     e = hkdf_sha256(m, ss_i, a->ss, a->ss, nullptr, 0, info, info_off ? info_off + off : nullptr, info_len,
                     key_len, key_i + off * key_len, key_len, st);
     if (e != hipSuccess) return hip_fail("hkdf_sha256", e);

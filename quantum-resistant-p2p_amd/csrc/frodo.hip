@@ -1233,14 +1233,6 @@ size_t frodo_scratch_bytes(const AlgInfo& a, size_t chunk) {
   return 0;
 }
 
-#define QRK_FRODO_DISPATCH(CALL)                       \
-  switch (a.k) {                                       \
-    case 640: return frodo::CALL<640>;                 \
-    case 976: return frodo::CALL<976>;                 \
-    case 1344: return frodo::CALL<1344>;               \
-  }                                                    \
-  return hipErrorInvalidValue
-
 hipError_t frodo_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
                          const Streams& s) {
   if (n == 0) return hipSuccess;
@@ -1256,7 +1248,7 @@ hipError_t frodo_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, c
 }
 
 hipError_t frodo_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* coins,
-                        void* scratch, const Streams& s) {
+                        int32_t*, void* scratch, const Streams& s) {
   if (n == 0) return hipSuccess;
   switch (a.k * 2 + (a.aes ? 1 : 0)) {
     case 1280: return frodo::encaps_t<640, false>(n, ct, ss, pk, coins, scratch, s.main);
@@ -1269,8 +1261,8 @@ hipError_t frodo_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, co
   return hipErrorInvalidValue;
 }
 
-hipError_t frodo_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, void* scratch,
-                        const Streams& s) {
+hipError_t frodo_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t*,
+                        void* scratch, const Streams& s) {
   if (n == 0) return hipSuccess;
   switch (a.k * 2 + (a.aes ? 1 : 0)) {
     case 1280: return frodo::decaps_t<640, false>(n, ss, ct, sk, scratch, s.main);

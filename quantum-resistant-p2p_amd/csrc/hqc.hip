@@ -1456,7 +1456,7 @@ hipError_t hqc_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, con
 }
 
 hipError_t hqc_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* coins,
-                      void* scratch, const Streams& s) {
+                      int32_t*, void* scratch, const Streams& s) {
   if (n == 0) return hipSuccess;
   switch (a.k) {
     case 128: return hqc::encaps_t<128>(n, ct, ss, pk, coins, scratch, s.main);

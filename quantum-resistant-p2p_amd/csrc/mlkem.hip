@@ -220,7 +220,7 @@ struct XofArgs {
   size_t rho_stride, n, C;
   XUnit* out;
   uint32_t *fix, *nfix;  // the fix-up list and its counter
-  uint32_t* zero_next;   // main pass (chunks <= DIRECT_RHO_MAX): the counter the next call counts into
+  uint32_t* zero_other;  // main pass (chunks <= DIRECT_RHO_MAX): the counter the next call counts into
 };
 // block vb of nvb (FIX: the grid-stride walk over the list uses nvb)
 template <int K, bool FIX>
@@ -228,7 +228,7 @@ __device__ __forceinline__ void xof_body(const XofArgs<K, FIX>& a, unsigned vb, 
   const uint32_t rb = ((threadIdx.x >> 6) * 16 * 64 + (threadIdx.x & 63)) * 4;  // ring_all: [wave][16][64]
   char* ring = (char*)ring_all;
   if constexpr (!FIX) {
-    if (vb == 0 && threadIdx.x == 0 && a.zero_next) *a.zero_next = 0u;
+    if (vb == 0 && threadIdx.x == 0 && a.zero_other) *a.zero_other = 0u;
     const size_t e = (size_t)vb * 256 + threadIdx.x, hs = e % a.C;
     if (e >= (size_t)K * K * a.C || hs >= a.n) return;
     const int xy = (int)(e / a.C);
@@ -2302,11 +2302,11 @@ void launch_multi(const char* name, std::initializer_list<const char*> names, co
 struct RhoSrc {
   const uint8_t* base;
   size_t stride;
-  uint32_t *nfix, *zero_next;
+  uint32_t *nfix, *zero_other;
 };
 template <int K>
 RXof<K, false> xof_role(const RhoSrc& r, size_t n, size_t C, const ScratchView& v) {
-  return {{r.base, r.stride, n, C, (XUnit*)v.xof, v.fix, r.nfix, r.zero_next}, blocks_for((size_t)K * K * C)};
+  return {{r.base, r.stride, n, C, (XUnit*)v.xof, v.fix, r.nfix, r.zero_other}, blocks_for((size_t)K * K * C)};
 }
 template <int K>
 RXof<K, true> fix_role(const RhoSrc& r, size_t n, size_t C, const ScratchView& v) {
@@ -2359,7 +2359,8 @@ inline RhoSrc rho_source(const uint8_t* keys_rho, size_t key_stride, size_t n, s
   if (C <= DIRECT_RHO_MAX && s.fixc && s.fixp) {
     const int p = *s.fixp;
     *s.fixp = p ^ 1;  // the next call counts into the word this call's main pass zeroes
-    if (g_dbg_fail_after_flip) qrk_chk(hipErrorLaunchFailure);  // tests only: a failure after the flip
+    // tests only: a failure after the flip
+    if (g_dbg_fail_after_flip.load(std::memory_order_relaxed)) qrk_chk(hipErrorLaunchFailure);
     return {keys_rho, key_stride, s.fixc + p, s.fixc + (p ^ 1)};
   }
   // k_xof reads rho from the compact copy in scratch
@@ -2388,7 +2389,7 @@ hipError_t keygen_impl(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
   if (QRK_KG_PIPE && n <= QRK_KG_MULTI_MAX && s.kg_cnt && s.kg_err) {  // host-pointer calls
     QRK_LAUNCH("k_keygen_pipe", s.main, k_keygen_pipe<K>, dim3((unsigned)(n * 3 * K)), dim3(64 * (K + 2)), 0, s.main, n,
                coins, pk, sk, (PipeScr*)scratch, s.kg_cnt, n == 1 ? s.done : nullptr, s.ticket, s.kg_err,
-               g_kg_dbg_late);
+               g_kg_dbg_late.load(std::memory_order_relaxed));
     return hipGetLastError();
   }
   if (n <= QRK_KG_MULTI_MAX && s.kg_cnt) {  // device-pointer calls (no error word), QRK_KG_PIPE=0 builds
@@ -2517,8 +2518,8 @@ size_t mlkem_kg_flag_words() { return (size_t)QRK_KG_MULTI_MAX * mlkem::KG_FLAGS
 size_t mlkem_kg_scratch_bytes() {
   return (size_t)QRK_KG_MULTI_MAX * std::max(sizeof(mlkem::MkScr), sizeof(mlkem::PipeScr));
 }
-int g_kg_dbg_late = -1;
-int g_dbg_fail_after_flip = 0;
+std::atomic<int> g_kg_dbg_late{-1};
+std::atomic<int> g_dbg_fail_after_flip{0};
 
 size_t mlkem_small_max() { return QRK_SMALL_MAX; }
 size_t mlkem_kg_multi_max() { return QRK_KG_MULTI_MAX; }
@@ -2560,7 +2561,7 @@ hipError_t mlkem_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, co
   return hipErrorInvalidValue;
 }
 
-hipError_t mlkem_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
+hipError_t mlkem_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t*,
                         void* scratch, const Streams& st) {
   if (n == 0) return hipSuccess;
   switch (a.k) {

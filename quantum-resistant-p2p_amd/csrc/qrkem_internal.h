@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace qrk {
 
 enum class Family { MLKEM, FRODO, HQC };
@@ -21,8 +23,6 @@ struct AlgInfo {
 };
 
 const AlgInfo* find_alg(const char* name);
-int alg_count();
-const AlgInfo* alg_at(int i);
 
 // Optional per-kernel HIP-event timing (qrk_ctx_profile): when a context has
 // profiling enabled, every QRK_LAUNCH brackets the launch with two events on the
@@ -55,12 +55,6 @@ inline void qrk_chk(hipError_t e) {
     if (::qrk::g_timer) ::qrk::g_timer->after(NAME, ST);  \
   } while (0)
 
-// Device scratch owned by a context.  Grown on demand, never shrunk.
-struct Scratch {
-  void* base = nullptr;
-  size_t bytes = 0;
-};
-
 // Per-chunk scratch requirement (bytes) for `chunk` handshakes of `a`.
 size_t mlkem_scratch_bytes(const AlgInfo& a, size_t chunk);
 size_t frodo_scratch_bytes(const AlgInfo& a, size_t chunk);
@@ -83,11 +77,12 @@ size_t mlkem_matrix_bytes(const AlgInfo& a, size_t chunk);
 // bytes at the start of the scratch that the n <= mlkem_kg_multi_max() KeyGen kernels use
 size_t mlkem_kg_scratch_bytes();
 // tests only (qrk_dbg_kg_late): the k_keygen_pipe workgroup role (PRF item or t_hat row) that
-// publishes past every bounded wait, -1 (default) none
-extern int g_kg_dbg_late;
+// publishes past every bounded wait, -1 (default) none.  Both switches are read (relaxed) at launch
+// by whichever thread drives a context while a test thread writes them.
+extern std::atomic<int> g_kg_dbg_late;
 // tests only (qrk_dbg_fail_after_flip): batched ML-KEM Encaps / Decaps chunks <= 2^15 fail right after
 // the fix-up counter parity flip, before any launch (0 = off)
-extern int g_dbg_fail_after_flip;
+extern std::atomic<int> g_dbg_fail_after_flip;
 hipError_t frodo_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st);
 hipError_t hqc_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st);
 
@@ -128,27 +123,29 @@ struct Streams {
 };
 
 // All pointers are device pointers; n handshakes processed as one chunk
-// (the caller splits large batches).  Return hipError_t.
+// (the caller splits large batches).  Return hipError_t.  The three families share one signature
+// per operation (abi.cpp keeps them in a table): `status` may be NULL, and a launcher that reports
+// nothing ignores it.  ML-KEM Encaps writes status[i] = -1 when ek fails the FIPS 203 modulus check,
+// HQC Decaps when the re-encryption check fails (ss = K(sigma || ct) is still written, the
+// OQS_KEM_decaps return of liboqs), and both write 0 otherwise.
 hipError_t mlkem_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
                          void* scratch, const Streams& st);
 hipError_t mlkem_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk,
                         const uint8_t* coins, int32_t* status, void* scratch, const Streams& st);
 hipError_t mlkem_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
-                        void* scratch, const Streams& st);
+                        int32_t* status, void* scratch, const Streams& st);
 
 hipError_t frodo_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
                          void* scratch, const Streams& st);
 hipError_t frodo_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk,
-                        const uint8_t* coins, void* scratch, const Streams& st);
+                        const uint8_t* coins, int32_t* status, void* scratch, const Streams& st);
 hipError_t frodo_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
-                        void* scratch, const Streams& st);
+                        int32_t* status, void* scratch, const Streams& st);
 
-// HQC: decaps writes status[i] = -1 when the re-encryption check fails (ss = K(sigma || ct) is
-// still written), the OQS_KEM_decaps return of liboqs; status may be NULL.
 hipError_t hqc_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
                        const Streams& st);
 hipError_t hqc_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* coins,
-                      void* scratch, const Streams& st);
+                      int32_t* status, void* scratch, const Streams& st);
 hipError_t hqc_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, int32_t* status,
                       void* scratch, const Streams& st);
 // Fixed-weight supports from n vectors of random words r[n][w] (kind 0: w = the key weight,
