@@ -226,6 +226,37 @@ int qrk_handshake_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
                         const uint64_t *info_off, size_t info_len, size_t key_len, uint8_t *pk_i, uint8_t *pk_r,
                         uint8_t *ct, uint8_t *key_i, uint8_t *key_r, int32_t *agree, void *stream);
 
+/* Authenticated encryption under n session keys, one GPU lane per message: what the reference does
+ * with every derived key (SymmetricAlgorithm.encrypt / decrypt, crypto/symmetric.py:95-161, 193-259),
+ * first for the key_exchange_test message that completes a handshake (messaging.py:1102-1114,
+ * 1224-1250).  alg: "AES-256-GCM" (SP 800-38D, 96-bit IV, 128-bit tag) or "ChaCha20-Poly1305"
+ * (RFC 8439), the reference's `name` strings; any other name returns -1.  Device pointers, of the
+ * kinds qrk_hkdf_sha256_batch accepts: keys [n][32]; nonces [n][12], or NULL for n nonces from the OS
+ * CSPRNG (the call then returns once they are uploaded, as with coins == NULL; never seal two messages
+ * under one key with one nonce); messages are ragged: bytes plus device uint64[n+1] offsets; aad /
+ * aad_off / aad_len as info / info_off / info_len of qrk_hkdf_sha256_batch (all NULL / 0: no
+ * associated data).  Row lengths are 32-bit: aad_len >= 2^31 returns -1.
+ *
+ * Seal: row i of `sealed` = nonce || ciphertext || tag, exactly the bytes `encrypt` returns
+ * (symmetric.py:116-119), at byte pt_off[i] + 28 i; `sealed` holds pt_off[n] + 28 n bytes.  A row whose
+ * plaintext or aad span is 2^31 bytes or more is left unwritten.
+ * Open: row i = sealed[sealed_off[i] .. sealed_off[i+1]); its plaintext goes to byte
+ * sealed_off[i] - 28 i of `pt`, which holds sealed_off[n] - 28 bytes (sealed_off[n] - 28 n are used
+ * when every row has its 28 bytes of overhead).  status (device int32[n], required): 0, or -1 for a row shorter than 28 bytes, of 2^31
+ * bytes or more, or whose tag does not verify.  The tag is computed and compared (without early exit)
+ * before any plaintext is written; where it does not match, zeros are written over that row's plaintext
+ * span: no unauthenticated plaintext is released.  A row shorter than 28 bytes writes nothing; the
+ * offset rule then places the following rows' plaintext up to 28 bytes early, over the tail of the
+ * preceding one (a row whose place would start before `pt` gets status -1), so a caller that cannot
+ * rule such rows out pads them to 28 bytes (they fail to verify).
+ * Authentication failure is reported only in status; the calls return 0 / -1 as the rest of Part 2. */
+int qrk_aead_seal_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *nonces,
+                        const uint8_t *pt, const uint64_t *pt_off, const uint8_t *aad, const uint64_t *aad_off,
+                        size_t aad_len, uint8_t *sealed, void *stream);
+int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *sealed,
+                        const uint64_t *sealed_off, const uint8_t *aad, const uint64_t *aad_off, size_t aad_len,
+                        uint8_t *pt, int32_t *status, void *stream);
+
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853
  * ciphertext and responder key; decoded at :829 with base64.b64decode).  Device pointers,

@@ -1184,6 +1184,94 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   return 0;
 }
 
+// "AES-256-GCM" / "ChaCha20-Poly1305": the reference's SymmetricAlgorithm.name strings (symmetric.py:72, 170)
+static int resolve_aead(const char* alg, AeadAlg* out) {
+  if (alg && !strcmp(alg, "AES-256-GCM")) return *out = AeadAlg::AES_256_GCM, 0;
+  if (alg && !strcmp(alg, "ChaCha20-Poly1305")) return *out = AeadAlg::CHACHA20_POLY1305, 0;
+  return fail(std::string("unsupported AEAD: ") + (alg ? alg : "(null)"));
+}
+
+int qrk_aead_seal_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* keys, const uint8_t* nonces,
+                        const uint8_t* pt, const uint64_t* pt_off, const uint8_t* aad, const uint64_t* aad_off,
+                        size_t aad_len, uint8_t* sealed, void* stream) {
+  if (!ctx) return fail("null context");
+  AeadAlg which;
+  if (resolve_aead(alg, &which)) return -1;
+  if (n == 0) return 0;
+  if (!keys || !pt || !pt_off || !sealed || (!aad && (aad_off || aad_len))) return fail("null buffer");
+  if (aad_len >> 31) return fail("AEAD row lengths are 32-bit: aad_len must be below 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard device_guard;
+  if (device_guard.set(ctx->device)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  // nonces == NULL: n fresh 96-bit nonces from the OS CSPRNG (os.urandom(12), symmetric.py:110, 208),
+  // staged and wiped like OS-drawn coins (run_batch).  The staging belongs to the context, so the call
+  // is ordered behind the context's previous one and recorded as its last use.
+  if (ctx_order(ctx, st)) return -1;
+  LastUse last_use{ctx, st};
+  CoinWipe nonce_wipe{ctx, st};
+  if (!nonces) {
+    const size_t bytes = n * 12;
+    if (grow_pinned(&ctx->hstage, &ctx->hstage_bytes, bytes)) return -1;
+    if (grow_device(ctx, (void**)&ctx->dstage, &ctx->dstage_bytes, bytes, st)) return -1;
+    if (!ctx->ev_up) {
+      hipError_t e = hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming);
+      if (e != hipSuccess) return hip_fail("hipEventCreate(upload)", e);
+    }
+    if (os_random(ctx->hstage, bytes)) return -1;
+    nonce_wipe.bytes = bytes;
+    hipError_t e = hipMemcpyAsync(ctx->dstage, ctx->hstage, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev_up, st);
+    if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_up);
+    OQS_MEM_cleanse(ctx->hstage, bytes);
+    if (e != hipSuccess) return hip_fail("hipMemcpyAsync(nonces)", e);
+    nonces = ctx->dstage;
+  }
+  g_launch_err = hipSuccess;
+  (void)hipGetLastError();
+  hipError_t e = aead_seal(which, n, keys, nonces, pt, pt_off, aad, aad_off, aad_len, sealed, st);
+  if (e == hipSuccess) e = g_launch_err;
+  return e == hipSuccess ? 0 : hip_fail("aead_seal", e);
+}
+
+int qrk_aead_open_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* keys, const uint8_t* sealed,
+                        const uint64_t* sealed_off, const uint8_t* aad, const uint64_t* aad_off, size_t aad_len,
+                        uint8_t* pt, int32_t* status, void* stream) {
+  if (!ctx) return fail("null context");
+  AeadAlg which;
+  if (resolve_aead(alg, &which)) return -1;
+  if (n == 0) return 0;
+  if (!keys || !sealed || !sealed_off || !pt || !status || (!aad && (aad_off || aad_len))) return fail("null buffer");
+  if (aad_len >> 31) return fail("AEAD row lengths are 32-bit: aad_len must be below 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard device_guard;
+  if (device_guard.set(ctx->device)) return -1;
+  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  g_launch_err = hipSuccess;
+  (void)hipGetLastError();
+  hipError_t e = aead_open(which, n, keys, sealed, sealed_off, aad, aad_off, aad_len, pt, status, (hipStream_t)stream);
+  if (e == hipSuccess) e = g_launch_err;
+  return e == hipSuccess ? 0 : hip_fail("aead_open", e);
+}
+
+// Tests only (not in qrkem.h): Poly1305 and GHASH on chosen keys.  Through the AEADs r, s and H are
+// cipher outputs and cannot be steered to their edge cases (r = 1 with an accumulator of exactly p + k,
+// single-bit and all-ones H).  Device pointers; tag_i = Poly1305(key32_i = r | s, msg_i), msg ragged by
+// msg_off [n+1]; out_i = GHASH_{h_i}(data_i), data_i a whole number of 16-byte blocks.
+extern "C" int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off,
+                                      uint8_t* tag, void* stream) {
+  if (n && (!key32 || !msg || !msg_off || !tag)) return fail("null buffer");
+  hipError_t e = dbg_poly1305(n, key32, msg, msg_off, tag, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail("dbg_poly1305", e);
+}
+extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off,
+                                   uint8_t* out, void* stream) {
+  if (n && (!h || !data || !data_off || !out)) return fail("null buffer");
+  hipError_t e = dbg_ghash(n, h, data, data_off, out, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail("dbg_ghash", e);
+}
+
 int qrk_base64_encode_batch(qrk_ctx* ctx, size_t n, const uint8_t* in, size_t in_len, uint8_t* out, void* stream) {
   if (!ctx) return fail("null context");
   if (n && in_len && (!in || !out)) return fail("null buffer");

@@ -175,6 +175,23 @@ hipError_t hkdf_sha256(size_t n, const uint8_t* ikm, size_t ikm_len, size_t ikm_
 // agree_i = (a_i == b_i), len bytes each
 hipError_t keys_equal(size_t n, const uint8_t* a, const uint8_t* b, size_t len, int32_t* agree, hipStream_t st);
 
+// AEAD over n messages, one lane per message (aead.hip).  keys [n][32]; nonces [n][12]; ragged bytes with
+// n+1 offsets; aad_off may be NULL (every row uses aad[0 .. aad_len)).  Seal writes row i = nonce | ct |
+// tag at pt_off[i] + 28 i; Open reads rows by sealed_off, writes plaintext i at sealed_off[i] - 28 i
+// (zeros where the tag does not match) and status[i] = 0 / -1.
+enum class AeadAlg { AES_256_GCM, CHACHA20_POLY1305 };
+hipError_t aead_seal(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* nonces, const uint8_t* pt,
+                     const uint64_t* pt_off, const uint8_t* aad, const uint64_t* aad_off, size_t aad_len,
+                     uint8_t* sealed, hipStream_t st);
+hipError_t aead_open(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* sealed, const uint64_t* sealed_off,
+                     const uint8_t* aad, const uint64_t* aad_off, size_t aad_len, uint8_t* pt, int32_t* status,
+                     hipStream_t st);
+// tests only: Poly1305 (key32 = r | s, any message length) and GHASH (whole blocks) on chosen inputs
+hipError_t dbg_poly1305(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off, uint8_t* tag,
+                        hipStream_t st);
+hipError_t dbg_ghash(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
+                     hipStream_t st);
+
 // Standard base64 (RFC 4648, '=' padding) of n records of L bytes -> [n][4 ceil(L/3)] chars,
 // and strict decoding back (status[i] = -1 for a malformed record; caller zeroes status).
 hipError_t base64_encode(size_t n, const uint8_t* in, size_t L, uint8_t* out, hipStream_t st);

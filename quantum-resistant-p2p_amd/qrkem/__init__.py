@@ -17,5 +17,18 @@ from .key_exchange import (  # noqa: F401
 )
 
 
+# The symmetric layer (crypto/symmetric.py's surface over aead.hip) is re-exported on first use:
+# its module needs torch for device buffers, which `import qrkem` alone does not load.
+_SYMMETRIC = ("SymmetricAlgorithm", "AES256GCM", "ChaCha20Poly1305")
+
+
+def __getattr__(name: str):
+    if name in _SYMMETRIC or name == "symmetric":
+        import importlib
+        mod = importlib.import_module(".symmetric", __name__)
+        return mod if name == "symmetric" else getattr(mod, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def device_count() -> int:
     return int(LIB.qrk_device_count())

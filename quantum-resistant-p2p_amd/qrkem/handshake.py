@@ -200,3 +200,27 @@ class HandshakeDriver:
         if rc != 0:
             raise RuntimeError(f"qrkem handshake batch failed ({self.alg}): {last_error()}")
         return out
+
+    def confirm(self, batch: HandshakeBatch, messages, nonces=None):
+        """The key confirmation that ends every exchange: the initiator seals a test message with its
+        new key (messaging.py:1102-1114) and the responder opens it with its own (:1224-1250), both
+        without associated data, under the driver's ``symmetric_name``.
+
+        ``messages``: n byte strings, an [n, L] device tensor or :class:`qrkem.symmetric.PackedRows`;
+        ``nonces``: [n, 12] or None (OS CSPRNG).  Returns ``(sealed, ok)``: the sealed rows in the form
+        of ``messages`` (nonce || ciphertext || tag each, the key_exchange_test payload before base64)
+        and int32 ``ok`` [n] on the device, 1 where ``batch.key_responder[i]`` opened row i.  The keys
+        are used where :meth:`run` left them, as device tensors."""
+        from . import symmetric as sym
+        e = self.engine
+        rows, kind = sym._rows_in(messages, self.device)
+        n = batch.key_initiator.shape[0]
+        if rows.n != n:
+            raise ValueError(f"{rows.n} messages for {n} handshakes")
+        if self.key_len != 32:
+            raise ValueError(f"{self.symmetric_name} keys are 32 bytes, this driver derives {self.key_len}")
+        if nonces is not None and not _is_dev(nonces):
+            nonces = _dev(_as_host(nonces, sym.NONCE_LEN), self.device)
+        sealed = sym.seal_rows(e._ctx, self.symmetric_name, self.device, batch.key_initiator, rows, None, nonces)
+        _opened, status = sym.open_rows(e._ctx, self.symmetric_name, self.device, batch.key_responder, sealed, None)
+        return sym._rows_out(sealed, kind), (status == 0).to(torch.int32)
