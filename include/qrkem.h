@@ -82,8 +82,10 @@ OQS_STATUS OQS_KEM_encaps_derand(const OQS_KEM *kem, uint8_t *ciphertext, uint8_
                                  const uint8_t *public_key, const uint8_t *seed);
 
 /* Signature half of the liboqs ABI: the reference's oqs.py binds these at
- * import time (oqs.py:684-697).  Signatures are outside this engine's scope,
- * so the registry is empty (count 0) and every call fails. */
+ * import time (oqs.py:684-697).  The engine has no KeyGen or Sign, and an
+ * OQS_SIG that could only verify would be a trap, so the registry stays empty
+ * (count 0) and every call here fails.  Batched ML-DSA verification is
+ * qrk_sig_verify_batch in Part 2. */
 typedef struct OQS_SIG OQS_SIG;
 size_t OQS_SIG_alg_count(void);
 const char *OQS_SIG_alg_identifier(size_t i);
@@ -256,6 +258,23 @@ int qrk_aead_seal_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
 int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *sealed,
                         const uint64_t *sealed_off, const uint8_t *aad, const uint64_t *aad_off, size_t aad_len,
                         uint8_t *pt, int32_t *status, void *stream);
+
+/* ML-DSA signature verification (FIPS 204 final, "pure" ML-DSA: Verify, Algorithm 3), the step the
+ * reference runs on every handshake and chat message (signatures.py:167 from messaging.py:721, 933,
+ * 1174, 1480).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; any other name returns -1 with
+ * qrk_last_error() set.  Verification only: there is no KeyGen or Sign (the OQS_SIG registry of
+ * Part 1 stays empty).
+ * out[0..2] = public key, secret key, signature bytes; -1 for an unknown name. */
+int qrk_sig_sizes(const char *alg, size_t out[3]);
+/* n verifications.  Device pointers: pk [n][pk bytes], sig [n][sig bytes], messages ragged (bytes +
+ * uint64[n+1] offsets, as qrk_aead_*), ctx_str / ctx_len one context string for all rows (NULL / 0 =
+ * empty, what liboqs's OQS_SIG_sign uses; ctx_len > 255 returns -1).
+ * status (required, int32[n]): 0 valid, -1 otherwise; every row is written exactly once.  A row of
+ * 2^31 bytes or more gets -1.  Stream-ordered on `stream`; uses the context's scratch (k l KiB + about
+ * 1.3 KB per row, grown on demand; qrk_ctx_set_chunk bounds the rows per launch). */
+int qrk_sig_verify_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *pk, const uint8_t *msg,
+                         const uint64_t *msg_off, const uint8_t *sig, const uint8_t *ctx_str, size_t ctx_len,
+                         int32_t *status, void *stream);
 
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853

@@ -777,7 +777,7 @@ OQS_STATUS OQS_KEM_decaps(const OQS_KEM* kem, uint8_t* ss, const uint8_t* ct, co
 }
 void OQS_KEM_free(OQS_KEM* kem) { free(kem); }
 
-// Empty signature registry (see include/qrkem.h)
+// Empty signature registry (see include/qrkem.h: verification is qrk_sig_verify_batch, Part 2)
 size_t OQS_SIG_alg_count(void) { return 0; }
 const char* OQS_SIG_alg_identifier(size_t) { return nullptr; }
 int OQS_SIG_alg_is_enabled(const char*) { return 0; }
@@ -1270,6 +1270,77 @@ extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* da
   if (n && (!h || !data || !data_off || !out)) return fail("null buffer");
   hipError_t e = dbg_ghash(n, h, data, data_off, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("dbg_ghash", e);
+}
+
+// ------------------------------------------------------------------ ML-DSA verification (mldsa.hip)
+int qrk_sig_sizes(const char* alg, size_t out[3]) {
+  const int which = mldsa_find(alg);
+  if (which < 0 || !out) return fail(std::string("unsupported signature algorithm: ") + (alg ? alg : "(null)"));
+  size_t s[4];
+  mldsa_sizes(which, s);
+  out[0] = s[0], out[1] = s[1], out[2] = s[2];
+  return 0;
+}
+
+// The scratch is k l KiB + about 1.3 KB per row (A_hat, mu, w1, c, flags): chunks are capped like the
+// families' (chunk_for) and run as equal multiples of 64 with a shorter tail.
+static int sig_verify(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                      const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                      int32_t* status, const MldsaTrace& trace, void* stream) {
+  if (!ctx) return fail("null context");
+  const int which = mldsa_find(alg);
+  if (which < 0) return fail(std::string("unsupported signature algorithm: ") + (alg ? alg : "(null)"));
+  if (ctx_len > 255) return fail("ML-DSA context strings are at most 255 bytes");
+  if (n == 0) return 0;
+  if (!pk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard device_guard;
+  if (device_guard.set(ctx->device)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (ctx_order(ctx, st)) return -1;
+  LastUse last_use{ctx, st};
+  size_t sz[4];
+  mldsa_sizes(which, sz);
+  const size_t per_row = mldsa_scratch_bytes(which, 1);
+  const size_t cap = std::min({ctx->chunk, (size_t)1 << 20,
+                               std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_row / 64 * 64)});
+  const size_t nchunks = (n + cap - 1) / cap;
+  const size_t chunk = std::min(cap, ((n + nchunks - 1) / nchunks + 63) & ~(size_t)63);
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, mldsa_scratch_bytes(which, chunk), st)) return -1;
+  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = std::min(chunk, n - off);
+    MldsaTrace t = trace;
+    if (t.flags) t.mu += off * 64, t.ctilde += off * 64, t.w1 += off * sz[3], t.flags += off;
+    g_launch_err = hipSuccess;
+    (void)hipGetLastError();
+    hipError_t e = mldsa_verify(which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str, ctx_len,
+                                status + off, t, ctx->scratch, st);
+    if (e == hipSuccess) e = g_launch_err;
+    if (e != hipSuccess) return hip_fail("mldsa_verify", e);
+  }
+  return 0;
+}
+
+int qrk_sig_verify_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                         const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                         int32_t* status, void* stream) {
+  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, MldsaTrace{}, stream);
+}
+
+// Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed
+// c~' [n][64] (lambda / 4 bytes, then zeros), the w1Encode bytes [n][k 32 (6 or 4)] and a flag word
+// (bit 0: hint encoding malformed, bit 1: ||z||_inf >= gamma1 - beta, bit 2: c~ != c~'; bit 3, internal:
+// a row of 2^31 bytes or more).  A row with bit 0 or bit 3 set has zeros in the other three.  This is
+// what makes parity with tests/mldsa_spec.py byte-level instead of one boolean per row.
+extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk,
+                                          const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
+                                          const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
+                                          uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream) {
+  if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
+  MldsaTrace t;
+  t.mu = mu, t.ctilde = ctilde, t.w1 = w1, t.flags = flags;
+  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
 }
 
 int qrk_base64_encode_batch(qrk_ctx* ctx, size_t n, const uint8_t* in, size_t in_len, uint8_t* out, void* stream) {

@@ -192,6 +192,24 @@ hipError_t dbg_poly1305(size_t n, const uint8_t* key32, const uint8_t* msg, cons
 hipError_t dbg_ghash(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                      hipStream_t st);
 
+// ML-DSA.Verify over n rows of one chunk (mldsa.hip; FIPS 204, pure ML-DSA).  which = mldsa_find(name):
+// 0, 1, 2 for ML-DSA-44 / 65 / 87, -1 for any other name.  pk [n][pk], sig [n][sig], messages ragged
+// (msg + n + 1 offsets), one context string of ctx_len <= 255 bytes for all rows (device pointer; not
+// read when ctx_len = 0).  status[i] = 0 (valid) or -1, written for every row.  The trace pointers are
+// all set or all NULL (tests): mu [n][64] and ctilde [n][64] 8-byte aligned, w1 [n][w1 bytes], flags [n].
+struct MldsaTrace {
+  uint8_t* mu = nullptr;
+  uint8_t* ctilde = nullptr;
+  uint8_t* w1 = nullptr;
+  uint32_t* flags = nullptr;
+};
+int mldsa_find(const char* name);
+void mldsa_sizes(int which, size_t out[4]);  // pk, sk, sig, w1Encode bytes
+size_t mldsa_scratch_bytes(int which, size_t chunk);
+hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* msg, const uint64_t* msg_off,
+                        const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
+                        const MldsaTrace& trace, void* scratch, hipStream_t st);
+
 // Standard base64 (RFC 4648, '=' padding) of n records of L bytes -> [n][4 ceil(L/3)] chars,
 // and strict decoding back (status[i] = -1 for a malformed record; caller zeroes status).
 hipError_t base64_encode(size_t n, const uint8_t* in, size_t L, uint8_t* out, hipStream_t st);

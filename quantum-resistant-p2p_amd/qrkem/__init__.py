@@ -20,6 +20,8 @@ from .key_exchange import (  # noqa: F401
 # The symmetric layer (crypto/symmetric.py's surface over aead.hip) is re-exported on first use:
 # its module needs torch for device buffers, which `import qrkem` alone does not load.
 _SYMMETRIC = ("SymmetricAlgorithm", "AES256GCM", "ChaCha20Poly1305")
+# ... and so is the signature layer (crypto/signatures.py's surface over mldsa.hip: verification only)
+_SIGNATURES = ("SignatureAlgorithm", "MLDSASignature")
 
 
 def __getattr__(name: str):
@@ -27,6 +29,10 @@ def __getattr__(name: str):
         import importlib
         mod = importlib.import_module(".symmetric", __name__)
         return mod if name == "symmetric" else getattr(mod, name)
+    if name in _SIGNATURES or name == "signatures":
+        import importlib
+        mod = importlib.import_module(".signatures", __name__)
+        return mod if name == "signatures" else getattr(mod, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

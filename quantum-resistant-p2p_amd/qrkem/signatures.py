@@ -1,0 +1,160 @@
+"""ML-DSA signature verification on the GPU -- the verifying half of the reference's ``crypto/signatures.py``.
+
+``SignatureAlgorithm`` keeps the three abstract methods of ``quantum_resistant_p2p/crypto/signatures.py:
+18-55`` and ``MLDSASignature`` the names, strings and errors of ``:58-188``.  Only ``verify`` is
+implemented (``qrk_sig_verify_batch``, mldsa.hip: FIPS 204 pure ML-DSA with the empty context string,
+what liboqs's ``OQS_SIG_sign`` produces); ``generate_keypair`` and ``sign`` raise ``NotImplementedError``:
+a node keeps signing with liboqs and verifies the messages it receives here, in batches
+(:meth:`MLDSASignature.verify_batch`).  Like ``_native.py`` there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import abc
+import ctypes as ct
+import logging
+from typing import Tuple
+
+import numpy as np
+
+from ._native import LIB, last_error
+from .algorithm_base import CryptoAlgorithm
+from .batch import _as_host, _check_dev, _is_dev
+from .handshake import _dev, _ptr, pack_infos
+
+try:
+    import torch
+except ImportError:  # pragma: no cover
+    torch = None
+
+logger = logging.getLogger(__name__)
+
+VERIFY_ONLY = ("qrkem verifies ML-DSA signatures only: {} stays with liboqs "
+               "(libqrkem has no ML-DSA KeyGen or Sign)")
+
+
+class SignatureAlgorithm(CryptoAlgorithm):
+    """Same abstract surface as crypto/signatures.py:18-55."""
+
+    @abc.abstractmethod
+    def generate_keypair(self) -> Tuple[bytes, bytes]:
+        ...
+
+    @abc.abstractmethod
+    def sign(self, private_key: bytes, message: bytes) -> bytes:
+        ...
+
+    @abc.abstractmethod
+    def verify(self, public_key: bytes, message: bytes, signature: bytes) -> bool:
+        ...
+
+
+def sig_sizes(variant: str) -> Tuple[int, int, int]:
+    """(public key, secret key, signature) bytes of an ML-DSA parameter set."""
+    out = (ct.c_size_t * 3)()
+    if LIB.qrk_sig_sizes(variant.encode(), out) != 0:
+        raise ValueError(last_error())
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+class MLDSASignature(SignatureAlgorithm):
+    """ML-DSA (FIPS 204) verification on one device.  The context is created on first use, so
+    constructing the object (as the reference does at start-up, messaging.py:128) needs no GPU."""
+
+    VARIANTS = {2: "ML-DSA-44", 3: "ML-DSA-65", 5: "ML-DSA-87"}
+
+    def __init__(self, security_level: int = 3, device: int = 0):
+        if security_level not in self.VARIANTS:
+            raise ValueError(f"Invalid security level: {security_level}. Must be 2, 3, or 5.")
+        self.security_level = security_level
+        self.variant = self.VARIANTS[security_level]
+        self.device = device
+        self.public_key_size, self.secret_key_size, self.signature_size = sig_sizes(self.variant)
+        self._ctx = None
+
+    @property
+    def name(self) -> str:
+        return f"ML-DSA (Level {self.security_level})"
+
+    @property
+    def display_name(self) -> str:
+        return f"ML-DSA (Level {self.security_level})"
+
+    @property
+    def description(self) -> str:
+        return ("ML-DSA is a lattice-based digital signature scheme. "
+                "It is one of the NIST post-quantum cryptography standards.")
+
+    def _context(self):
+        if self._ctx is None:
+            h = ct.c_void_p()
+            if LIB.qrk_ctx_create(ct.byref(h), self.device) != 0:
+                raise RuntimeError(f"qrkem: cannot create a context on device {self.device}: {last_error()}")
+            self._ctx = h
+        return self._ctx
+
+    def close(self) -> None:
+        if getattr(self, "_ctx", None):
+            LIB.qrk_ctx_destroy(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ the reference's single calls
+    def generate_keypair(self) -> Tuple[bytes, bytes]:
+        raise NotImplementedError(VERIFY_ONLY.format("key generation"))
+
+    def sign(self, private_key: bytes, message: bytes) -> bytes:
+        raise NotImplementedError(VERIFY_ONLY.format("signing"))
+
+    def verify(self, public_key: bytes, message: bytes, signature: bytes) -> bool:
+        """True if the signature is valid.  Never raises: a wrong-length key or signature is False
+        without any GPU work, and so is any error (logged), as in the reference (signatures.py:186-188)."""
+        try:
+            if len(public_key) != self.public_key_size or len(signature) != self.signature_size:
+                return False
+            return bool(self.verify_batch([bytes(public_key)], [bytes(message)], [bytes(signature)])[0])
+        except Exception as exc:
+            logger.error(f"Error verifying ML-DSA signature: {exc}")
+            return False
+
+    # ------------------------------------------------------------------ batches
+    def verify_batch(self, public_keys, messages, signatures, offsets=None):
+        """valid[i] = Verify(public_keys[i], messages[i], signatures[i]): a numpy bool array [n].
+
+        ``public_keys`` / ``signatures``: [n, pk bytes] / [n, signature bytes] uint8 (device tensors,
+        numpy arrays or lists of bytes).  ``messages``: a list of byte strings, or a 1-D uint8 device
+        tensor of the messages back to back with ``offsets``, an int64 or uint64 [n + 1] device
+        tensor (message i = messages[offsets[i]:offsets[i + 1]]).  Use :meth:`verify_status` to keep
+        the result on the device."""
+        return self.verify_status(public_keys, messages, signatures, offsets).cpu().numpy() == 0
+
+    def verify_status(self, public_keys, messages, signatures, offsets=None):
+        """As :meth:`verify_batch`, returning the int32 [n] device tensor of the C ABI: 0 valid, -1 not."""
+        ctx = self._context()  # first: without a device this is the error to raise
+        if offsets is None:
+            data, off = pack_infos([bytes(m) for m in messages])
+            messages, offsets = _dev(data, self.device), _dev(off.view(np.int64), self.device)
+        n = offsets.numel() - 1
+        if not (_is_dev(messages) and messages.dtype == torch.uint8 and messages.dim() == 1 and
+                messages.is_contiguous()):
+            raise ValueError("messages must be a contiguous 1-D uint8 device tensor")
+        if not (_is_dev(offsets) and offsets.dtype in (torch.int64, torch.uint64) and offsets.dim() == 1 and
+                n >= 0 and offsets.is_contiguous()):
+            raise ValueError("offsets must be a contiguous 64-bit device tensor of n + 1 entries")
+        if not _is_dev(public_keys):
+            public_keys = _dev(_as_host(public_keys, self.public_key_size), self.device)
+        if not _is_dev(signatures):
+            signatures = _dev(_as_host(signatures, self.signature_size), self.device)
+        _check_dev(public_keys, self.public_key_size, "ML-DSA public keys", n)
+        _check_dev(signatures, self.signature_size, "ML-DSA signatures", n)
+        status = torch.empty((n,), dtype=torch.int32, device=messages.device)
+        rc = LIB.qrk_sig_verify_batch(ctx, self.variant.encode(), n, _ptr(public_keys), _ptr(messages), _ptr(offsets),
+                                      _ptr(signatures), None, 0, _ptr(status),
+                                      ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"qrkem ML-DSA verify failed ({self.variant}): {last_error()}")
+        return status
