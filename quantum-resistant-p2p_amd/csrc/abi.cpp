@@ -105,7 +105,8 @@ static int hip_fail(const char* what, hipError_t e) {
 // ------------------------------------------------------------------ kernel timing
 namespace qrk {
 thread_local KernelTimer* g_timer = nullptr;
-thread_local hipError_t g_launch_err = hipSuccess;
+thread_local hipError_t g_launch_err{hipSuccess};
+std::atomic<int> g_dbg_fail_launch{0};
 }
 
 // Pairs of HIP events recorded on the launch stream around every kernel; read
@@ -211,10 +212,10 @@ static void ctx_quiesce(qrk_ctx* ctx) {
 }
 // Records the end of this call on `st` on every exit path, including early error returns.
 struct LastUse {
-  qrk_ctx* ctx;
-  hipStream_t st;
+  qrk_ctx* ctx = nullptr;  // null: not armed
+  hipStream_t st = nullptr;
   ~LastUse() {
-    if (hipEventRecord(ctx->ev_last, st) == hipSuccess) {
+    if (ctx && hipEventRecord(ctx->ev_last, st) == hipSuccess) {
       ctx->last_valid = true;
       ctx->last_stream = st;
     }
@@ -288,21 +289,6 @@ static const AlgInfo* resolve(const char* alg) {
   return nullptr;
 }
 
-// The opening of an ABI call on a context: null check, algorithm, context lock ...
-#define QRK_RESOLVE(ctx, alg)                \
-  if (!(ctx)) return fail("null context");   \
-  const AlgInfo* a = resolve(alg);           \
-  if (!a) return -1;                         \
-  std::lock_guard<std::mutex> lk((ctx)->mu);
-// ... and of a hook that reads a context's buffers back: null checks, context lock, its device
-// current, the previous call's device work complete
-#define QRK_INSPECT(ctx, args_ok)                           \
-  if (!(ctx) || !(args_ok)) return fail("null argument");   \
-  std::lock_guard<std::mutex> lk((ctx)->mu);                \
-  DeviceGuard device_guard;                                 \
-  if (device_guard.set((ctx)->device)) return -1;           \
-  ctx_quiesce(ctx);
-
 enum class Op { KEYPAIR, ENCAPS, DECAPS };
 
 // What one caller asks of one run_batch call beyond the batch itself.  Each option takes effect
@@ -330,14 +316,55 @@ static size_t chunk_for(const qrk_ctx* ctx, const AlgInfo& a) {
   return cap;
 }
 
-// Routes QRK_LAUNCH timing to the context's timer for the scope's lifetime (nests).
+// Equal chunks (multiples of 64) of at most `cap` handshakes rather than full chunks plus a small tail.
+static size_t round64(size_t n) { return (n + 63) & ~(size_t)63; }
+static size_t chunk_plan(size_t n, size_t cap) {
+  const size_t nchunks = (n + cap - 1) / cap;
+  return std::min(cap, round64((n + nchunks - 1) / nchunks));
+}
+
+// Routes QRK_LAUNCH timing to a timer (or to none) from set() to the end of the scope (nests).
 struct TimerScope {
-  KernelTimer* prev;
-  explicit TimerScope(KernelTimer* t) : prev(g_timer) { g_timer = t; }
+  KernelTimer* prev = g_timer;
+  void set(KernelTimer* t) { g_timer = t; }
   ~TimerScope() { g_timer = prev; }
 };
 
-// Zeroes the device staging copy of OS-drawn coins when run_batch returns (these are
+// The opening of every ABI call that launches, after its argument checks: the context lock, the
+// context's device current, the call ordered behind the context's last use and recorded as the new
+// one, kernel timing routed to the context's timer, the launch-error channel cleared -- in this
+// order, undone in reverse on every exit path.  An entry point names the parts it takes:
+//   LOCK   it is the outermost call on the context (run_batch runs under its caller's lock)
+//   ORDER  it reads or writes a buffer the context owns (scratch, staging)
+//   TIMER  its kernels count in the context's profile (qrk_ctx_profile)
+// and every one gets launch_begin(), so its launchers' return value is its answer.
+struct CallScope {
+  enum : unsigned { LOCK = 1, ORDER = 2, TIMER = 4 };
+  std::unique_lock<std::mutex> lk;
+  DeviceGuard device_guard;
+  LastUse last_use;
+  TimerScope timer_scope;
+  int open(qrk_ctx* ctx, hipStream_t st, unsigned parts) {
+    if (parts & LOCK) lk = std::unique_lock<std::mutex>(ctx->mu);
+    if (device_guard.set(ctx->device)) return -1;
+    if (parts & ORDER) {
+      if (ctx_order(ctx, st)) return -1;
+      last_use.ctx = ctx, last_use.st = st;
+    }
+    if (parts & TIMER) timer_scope.set(ctx->profiling ? &ctx->timer : nullptr);
+    launch_begin();
+    return 0;
+  }
+};
+// ... and of a hook that reads a context's buffers back: the previous call's device work complete
+static int open_inspect(CallScope& scope, qrk_ctx* ctx, bool args_ok) {
+  if (!ctx || !args_ok) return fail("null argument");
+  if (scope.open(ctx, nullptr, CallScope::LOCK)) return -1;
+  ctx_quiesce(ctx);
+  return 0;
+}
+
+// Zeroes the device staging copy of OS-drawn bytes when the call returns (coins are
 // the KeyGen seeds / Encaps messages, i.e. enough to rebuild the keys), stream-ordered after the
 // kernels that read it.  The pinned host copy is wiped as soon as its upload has completed.
 struct CoinWipe {
@@ -348,6 +375,24 @@ struct CoinWipe {
     if (bytes) (void)hipMemsetAsync(ctx->dstage, 0, bytes, st);
   }
 };
+// `bytes` from the OS CSPRNG in the context's device staging (NULL: failed), for a call on `st`
+// that holds `wipe`.  The one host wait of the device-pointer API: the pinned copy is wiped as soon
+// as it has reached the device, so the call returns after the upload (which the stream orders behind
+// its earlier work), not after the kernels.
+static const uint8_t* stage_os_random(qrk_ctx* ctx, size_t bytes, hipStream_t st, CoinWipe& wipe) {
+  if (grow_pinned(&ctx->hstage, &ctx->hstage_bytes, bytes)) return nullptr;
+  if (grow_device(ctx, (void**)&ctx->dstage, &ctx->dstage_bytes, bytes, st)) return nullptr;
+  hipError_t e = ctx->ev_up ? hipSuccess : hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming);
+  if (e != hipSuccess) return hip_fail("hipEventCreate(upload)", e), nullptr;
+  if (os_random(ctx->hstage, bytes)) return nullptr;
+  wipe.bytes = bytes;
+  e = hipMemcpyAsync(ctx->dstage, ctx->hstage, bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev_up, st);
+  if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_up);
+  OQS_MEM_cleanse(ctx->hstage, bytes);
+  if (e != hipSuccess) return hip_fail("hipMemcpyAsync(OS random bytes)", e), nullptr;
+  return ctx->dstage;
+}
 
 // Queues, on `st`, the re-zero of what a failed pipelined ML-KEM KeyGen may have left behind
 // (qrk_ctx::kg_dirty): its flag words and the head of the scratch its workgroups store to.
@@ -363,40 +408,19 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
                      const uint8_t* i2, int32_t* status, hipStream_t st, const CallOpts& opts) {
   if (n == 0) return 0;
   const FamilyOps& f = ops_of(a);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  if (ctx_order(ctx, st)) return -1;
-  LastUse last_use{ctx, st};
-  // equal chunks (multiples of 64) rather than full chunks plus a small tail
-  const size_t cap = chunk_for(ctx, a);
-  const size_t nchunks = (n + cap - 1) / cap;
-  const size_t chunk = std::min(cap, ((n + nchunks - 1) / nchunks + 63) & ~(size_t)63);
+  CallScope scope;  // the caller holds the lock
+  if (scope.open(ctx, st, CallScope::ORDER | CallScope::TIMER)) return -1;
+  const size_t chunk = chunk_plan(n, chunk_for(ctx, a));
   if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, f.scratch_bytes(a, chunk), st)) return -1;
   // coins: NULL -> OS CSPRNG, uploaded to device staging
   const uint8_t* coins = (op == Op::KEYPAIR) ? i1 : (op == Op::ENCAPS ? i2 : nullptr);
   const size_t clen = (op == Op::KEYPAIR) ? a.kp_coins : a.enc_coins;
   // OS coins are KeyGen seeds / Encaps messages: wipe both staged copies on every exit path
-  // (declared after last_use, so the device wipe is queued before the call's end event)
+  // (declared after the scope, so the device wipe is queued before the call's end event)
   CoinWipe coin_wipe{ctx, st};
   if (op != Op::DECAPS && coins == nullptr) {
-    // The one host wait of the device-pointer API: the pinned copy of the coins is wiped as soon
-    // as it has reached the device, so the call returns after the upload (which the stream
-    // orders behind its earlier work), not after the kernels.
-    const size_t bytes = n * clen;
-    if (grow_pinned(&ctx->hstage, &ctx->hstage_bytes, bytes)) return -1;
-    if (grow_device(ctx, (void**)&ctx->dstage, &ctx->dstage_bytes, bytes, st)) return -1;
-    if (!ctx->ev_up) {
-      hipError_t e = hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming);
-      if (e != hipSuccess) return hip_fail("hipEventCreate(upload)", e);
-    }
-    if (os_random(ctx->hstage, bytes)) return -1;
-    coin_wipe.bytes = bytes;
-    hipError_t e = hipMemcpyAsync(ctx->dstage, ctx->hstage, bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_up, st);
-    if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_up);
-    OQS_MEM_cleanse(ctx->hstage, bytes);
-    if (e != hipSuccess) return hip_fail("hipMemcpyAsync(coins)", e);
-    coins = ctx->dstage;
+    coins = stage_os_random(ctx, n * clen, st, coin_wipe);
+    if (!coins) return -1;
   }
   Streams S;
   S.main = st;
@@ -440,13 +464,11 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     S.fixc = ctx->fixc;
     S.fixp = &ctx->fixp;
   }
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
   HT(3);
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = std::min(chunk, n - off);
     hipError_t e = hipSuccess;
-    g_launch_err = hipSuccess;
-    (void)hipGetLastError();  // clear a stale error state (e.g. a caller's hipErrorNotReady query)
+    launch_begin();
     int32_t* const stat = status ? status + off : nullptr;
     switch (op) {
       case Op::KEYPAIR:
@@ -464,7 +486,6 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
         break;
     }
     HT(4);
-    if (e == hipSuccess) e = g_launch_err;
     if (e != hipSuccess) {
       ctx->fixc_dirty = S.fixc != nullptr;  // the counters' zero-between-calls invariant is unknown now
       return hip_fail("kernel launch", e);
@@ -827,9 +848,8 @@ static void cleanse_all(qrk_ctx* ctx) {
 
 int qrk_ctx_cleanse(qrk_ctx* ctx) {
   if (!ctx) return fail("null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
+  CallScope scope;
+  if (scope.open(ctx, nullptr, CallScope::LOCK)) return -1;
   cleanse_all(ctx);
   return 0;
 }
@@ -866,14 +886,15 @@ int qrk_ctx_set_streams(qrk_ctx* ctx, int streams) {
 int qrk_ctx_set_chunk(qrk_ctx* ctx, size_t chunk) {
   if (!ctx || chunk == 0) return fail("bad chunk");
   std::lock_guard<std::mutex> lk(ctx->mu);  // chunk_for reads it under the lock
-  ctx->chunk = (chunk + 63) & ~(size_t)63;
+  ctx->chunk = round64(chunk);
   return 0;
 }
 
 size_t qrk_ctx_scratch_bytes(const qrk_ctx* ctx) { return ctx ? ctx->scratch_bytes : 0; }
 
 int qrk_ctx_staging_residue(qrk_ctx* ctx, uint64_t out[3]) {
-  QRK_INSPECT(ctx, out);
+  CallScope scope;
+  if (open_inspect(scope, ctx, out)) return -1;
   out[0] = out[1] = out[2] = 0;
   for (size_t i = 0; i < ctx->hstage_bytes; ++i) out[0] += ctx->hstage[i] != 0;
   const void* src[2] = {ctx->dstage, ctx->scratch};
@@ -899,6 +920,15 @@ extern "C" int qrk_dbg_kg_late(int role) {
   return 0;
 }
 
+// Tests only (not in qrkem.h): every ABI call (every chunk of a chunked one) fails as if its first
+// launch had been rejected (0: off): launch_begin() records hipErrorLaunchFailure.  The kernels
+// themselves still launch, on valid buffers, except where a launcher stops at the first failure.
+// Process-wide.
+extern "C" int qrk_dbg_fail_launch(int on) {
+  g_dbg_fail_launch.store(on, std::memory_order_relaxed);
+  return 0;
+}
+
 // Tests only (not in qrkem.h): batched ML-KEM Encaps / Decaps chunks of at most 2^15 handshakes fail
 // right after the SampleNTT fix-up counter parity flip, before their first launch (0: off), and the
 // context's two fix-up counter words and its parity read back (the re-zero path).
@@ -907,7 +937,8 @@ extern "C" int qrk_dbg_fail_after_flip(int on) {
   return 0;
 }
 extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
-  QRK_INSPECT(ctx, out && parity);
+  CallScope scope;
+  if (open_inspect(scope, ctx, out && parity)) return -1;
   out[0] = out[1] = 0;
   *parity = ctx->fixp;
   if (!ctx->fixc) return 0;
@@ -918,7 +949,8 @@ extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
 // Tests only (not in qrkem.h): nonzero words among the context's single-shot KeyGen flag / counter
 // words, which must be zero between calls (after a failed pipelined KeyGen too).
 extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
-  QRK_INSPECT(ctx, out);
+  CallScope scope;
+  if (open_inspect(scope, ctx, out)) return -1;
   *out = 0;
   if (!ctx->kg_cnt) return 0;
   std::vector<uint32_t> tmp(mlkem_kg_flag_words());
@@ -930,11 +962,12 @@ extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
 // Tests only (not in qrkem.h): nonzero bytes left in the ML-KEM per-handshake records of a chunk
 // of n handshakes (mlkem_cleanse wipes them after every chunk).
 extern "C" int qrk_dbg_mlkem_records_residue(qrk_ctx* ctx, const char* alg, size_t n, uint64_t* out) {
-  QRK_INSPECT(ctx, out);
+  CallScope scope;
+  if (open_inspect(scope, ctx, out)) return -1;
   const AlgInfo* a = find_alg(alg);
   if (!a || a->family != Family::MLKEM) return fail("not an ML-KEM algorithm");
   size_t off = 0, bytes = 0;
-  mlkem_records_span(*a, (std::min(n, chunk_for(ctx, *a)) + 63) & ~(size_t)63, &off, &bytes);
+  mlkem_records_span(*a, round64(std::min(n, chunk_for(ctx, *a))), &off, &bytes);
   if (off + bytes > ctx->scratch_bytes) return fail("the context's scratch does not cover that chunk");
   std::vector<uint8_t> tmp(bytes);
   const hipError_t e = hipMemcpy(tmp.data(), (const char*)ctx->scratch + off, bytes, hipMemcpyDeviceToHost);
@@ -997,59 +1030,64 @@ int qrk_kem_sizes(const char* alg, size_t out[6]) {
   return 0;
 }
 
+// The KEM entry points: null check, algorithm, context lock, then the device-pointer driver on the
+// caller's stream or (host) the host-pointer wrapper on the context's own.
+static int kem_call(qrk_ctx* ctx, const char* alg, bool host, Op op, size_t n, uint8_t* o1, uint8_t* o2,
+                    const uint8_t* i1, const uint8_t* i2, int32_t* status, void* stream) {
+  if (!ctx) return fail("null context");
+  const AlgInfo* a = resolve(alg);
+  if (!a) return -1;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (host) return run_batch_host(ctx, *a, op, n, o1, o2, i1, i2, status);
+  return run_batch(ctx, *a, op, n, o1, o2, i1, i2, status, (hipStream_t)stream, {});
+}
 int qrk_kem_keypair_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
                           void* stream) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr, (hipStream_t)stream, {});
+  return kem_call(ctx, alg, false, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr, stream);
 }
 int qrk_kem_encaps_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk,
                          const uint8_t* coins, int32_t* status, void* stream) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::ENCAPS, n, ct, ss, pk, coins, status, (hipStream_t)stream, {});
+  return kem_call(ctx, alg, false, Op::ENCAPS, n, ct, ss, pk, coins, status, stream);
 }
 int qrk_kem_decaps_batch(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
                          void* stream) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, (hipStream_t)stream, {});
+  return kem_call(ctx, alg, false, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, stream);
 }
 int qrk_kem_decaps_batch_status(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                 const uint8_t* sk, int32_t* status, void* stream) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, status, (hipStream_t)stream, {});
+  return kem_call(ctx, alg, false, Op::DECAPS, n, ss, nullptr, ct, sk, status, stream);
 }
 int qrk_kem_keypair_batch_host(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* pk, uint8_t* sk,
                                const uint8_t* coins) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch_host(ctx, *a, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr);
+  return kem_call(ctx, alg, true, Op::KEYPAIR, n, pk, sk, coins, nullptr, nullptr, nullptr);
 }
 int qrk_kem_encaps_batch_host(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk,
                               const uint8_t* coins, int32_t* status) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch_host(ctx, *a, Op::ENCAPS, n, ct, ss, pk, coins, status);
+  return kem_call(ctx, alg, true, Op::ENCAPS, n, ct, ss, pk, coins, status, nullptr);
 }
 int qrk_kem_decaps_batch_host(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                               const uint8_t* sk) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch_host(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr);
+  return kem_call(ctx, alg, true, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, nullptr);
 }
 int qrk_kem_decaps_batch_status_host(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                      const uint8_t* sk, int32_t* status) {
-  QRK_RESOLVE(ctx, alg);
-  return run_batch_host(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, status);
+  return kem_call(ctx, alg, true, Op::DECAPS, n, ss, nullptr, ct, sk, status, nullptr);
 }
 
 int qrk_bench_coins(qrk_ctx* ctx, size_t n, size_t len, uint64_t seed, uint64_t first, uint8_t* out, void* stream) {
   if (!ctx) return fail("null context");
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
+  CallScope scope;  // no lock, no timer: bench.py's input generator, like qrk_tamper below
+  if (scope.open(ctx, (hipStream_t)stream, 0)) return -1;
   hipError_t e = bench_coins(n, len, seed, first, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("bench_coins", e);
 }
 
 int qrk_tamper(qrk_ctx* ctx, size_t n, size_t ctlen, uint64_t seed, int mode, uint8_t* ct, void* stream) {
   if (!ctx) return fail("null context");
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
+  // no lock (touches nothing of the context's); no timer: bench.py calls this inside its profiled,
+  // timed step, and timing it would change the reported profile
+  CallScope scope;
+  if (scope.open(ctx, (hipStream_t)stream, 0)) return -1;
   hipError_t e = tamper_ciphertexts(n, ctlen, seed, mode, ct, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("tamper", e);
 }
@@ -1058,44 +1096,40 @@ int qrk_digest_rows(qrk_ctx* ctx, size_t n, const uint8_t* a, size_t a_len, cons
                     uint8_t* out, void* stream) {
   if (!ctx) return fail("null context");
   if (n && (!a || !out || (b_len && !b))) return fail("null buffer");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  CallScope scope;
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK | CallScope::TIMER)) return -1;
   hipError_t e = digest_rows(n, a, a_len, b_len ? b : nullptr, b_len, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("digest_rows", e);
 }
 
 int qrk_hqc_supports(qrk_ctx* ctx, const char* alg, int kind, size_t n, const uint32_t* r, uint32_t* sup,
                      void* stream) {
-  QRK_RESOLVE(ctx, alg);
+  if (!ctx) return fail("null context");
+  const AlgInfo* a = resolve(alg);
+  if (!a) return -1;
   if (a->family != Family::HQC) return fail(std::string("not an HQC parameter set: ") + alg);
   if (kind != 0 && kind != 1) return fail("kind must be 0 (w) or 1 (w_r = w_e)");
   if (n && (!r || !sup)) return fail("null buffer");
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
+  CallScope scope;  // locked but untimed: k_hqc_supports has never counted in a context's profile
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK)) return -1;
   hipError_t e = hqc_supports(*a, kind, n, r, sup, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("hqc_supports", e);
 }
 
 int qrk_hqc_code_decode(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
                         uint8_t* mprime, void* stream) {
-  QRK_RESOLVE(ctx, alg);
+  if (!ctx) return fail("null context");
+  const AlgInfo* a = resolve(alg);
+  if (!a) return -1;
   if (a->family != Family::HQC) return fail(std::string("not an HQC parameter set: ") + alg);
   if (n == 0) return 0;
   if (!sk || !ct || !syms || !mprime) return fail("null buffer");
-  if (n > chunk_for(ctx, *a)) return fail("hqc_code_decode: n exceeds the context chunk");
   hipStream_t st = (hipStream_t)stream;
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  if (ctx_order(ctx, st)) return -1;
-  LastUse last_use{ctx, st};
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, ops_of(*a).scratch_bytes(*a, (n + 63) & ~(size_t)63), st)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
-  g_launch_err = hipSuccess;
-  (void)hipGetLastError();
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
+  if (n > chunk_for(ctx, *a)) return fail("hqc_code_decode: n exceeds the context chunk");
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, ops_of(*a).scratch_bytes(*a, round64(n)), st)) return -1;
   hipError_t e = hqc_code_decode(*a, n, sk, ct, syms, mprime, ctx->scratch, st);
-  if (e == hipSuccess) e = g_launch_err;
   if (e != hipSuccess) return hip_fail("hqc_code_decode", e);
   e = ops_of(*a).cleanse(*a, n, ctx->scratch, st);  // the symbols and m' do not outlive the call
   return e == hipSuccess ? 0 : hip_fail("hipMemsetAsync(cleanse)", e);
@@ -1108,10 +1142,8 @@ int qrk_hkdf_sha256_batch(qrk_ctx* ctx, size_t n, const uint8_t* ikm, size_t ikm
   if (okm_len == 0 || okm_len > 255 * 32) return fail("HKDF-SHA256 output length must be 1..8160 bytes");
   if (salt_len && !salt) return fail("salt_len > 0 with a NULL salt");
   if (n && (!ikm || !okm || (!info && (info_off || info_len)))) return fail("null buffer");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  CallScope scope;
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK | CallScope::TIMER)) return -1;
   hipError_t e = hkdf_sha256(n, ikm, ikm_len, ikm_len, salt, salt_len, info, info_off, info_len, okm_len, okm,
                              okm_len, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("hkdf_sha256", e);
@@ -1121,16 +1153,15 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
                         const uint8_t* coins_kp_r, const uint8_t* coins_enc, const uint8_t* info,
                         const uint64_t* info_off, size_t info_len, size_t key_len, uint8_t* pk_i, uint8_t* pk_r,
                         uint8_t* ct, uint8_t* key_i, uint8_t* key_r, int32_t* agree, void* stream) {
-  QRK_RESOLVE(ctx, alg);
+  if (!ctx) return fail("null context");
+  const AlgInfo* a = resolve(alg);
+  if (!a) return -1;
   if (key_len == 0 || key_len > 255 * 32) return fail("key_len must be 1..8160 bytes");
   if (n == 0) return 0;
   if (!pk_i || !pk_r || !ct || !key_i || !key_r) return fail("null output buffer");
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
-  if (ctx_order(ctx, st)) return -1;
-  LastUse last_use{ctx, st};
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
   // Ephemeral secrets of one chunk live in context scratch and are wiped afterwards
   // (the reference keeps them in Python objects: messaging.py:590-600, 809).
   const size_t chunk = chunk_for(ctx, *a);
@@ -1144,8 +1175,8 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   if (grow_device(ctx, (void**)&ctx->hs_scratch, &ctx->hs_scratch_bytes, 2 * b_sk + 2 * b_ss + b_mat, st)) return -1;
   uint8_t *sk_i = ctx->hs_scratch, *sk_r = sk_i + b_sk, *ss_i = sk_r + b_sk, *ss_r = ss_i + b_ss;
   uint64_t* mat_i = keep_a ? (uint64_t*)(ss_r + b_ss) : nullptr;
-  // wipes the ephemeral sk / ss on every exit path, error returns included (runs before
-  // last_use records the end of the call)
+  // wipes the ephemeral sk / ss on every exit path, error returns included (runs before the
+  // scope records the end of the call)
   struct Wipe {
     void* p;
     size_t bytes;
@@ -1200,38 +1231,18 @@ int qrk_aead_seal_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   if (n == 0) return 0;
   if (!keys || !pt || !pt_off || !sealed || (!aad && (aad_off || aad_len))) return fail("null buffer");
   if (aad_len >> 31) return fail("AEAD row lengths are 32-bit: aad_len must be below 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
   // nonces == NULL: n fresh 96-bit nonces from the OS CSPRNG (os.urandom(12), symmetric.py:110, 208),
   // staged and wiped like OS-drawn coins (run_batch).  The staging belongs to the context, so the call
   // is ordered behind the context's previous one and recorded as its last use.
-  if (ctx_order(ctx, st)) return -1;
-  LastUse last_use{ctx, st};
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
   CoinWipe nonce_wipe{ctx, st};
   if (!nonces) {
-    const size_t bytes = n * 12;
-    if (grow_pinned(&ctx->hstage, &ctx->hstage_bytes, bytes)) return -1;
-    if (grow_device(ctx, (void**)&ctx->dstage, &ctx->dstage_bytes, bytes, st)) return -1;
-    if (!ctx->ev_up) {
-      hipError_t e = hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming);
-      if (e != hipSuccess) return hip_fail("hipEventCreate(upload)", e);
-    }
-    if (os_random(ctx->hstage, bytes)) return -1;
-    nonce_wipe.bytes = bytes;
-    hipError_t e = hipMemcpyAsync(ctx->dstage, ctx->hstage, bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_up, st);
-    if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_up);
-    OQS_MEM_cleanse(ctx->hstage, bytes);
-    if (e != hipSuccess) return hip_fail("hipMemcpyAsync(nonces)", e);
-    nonces = ctx->dstage;
+    nonces = stage_os_random(ctx, n * 12, st, nonce_wipe);
+    if (!nonces) return -1;
   }
-  g_launch_err = hipSuccess;
-  (void)hipGetLastError();
   hipError_t e = aead_seal(which, n, keys, nonces, pt, pt_off, aad, aad_off, aad_len, sealed, st);
-  if (e == hipSuccess) e = g_launch_err;
   return e == hipSuccess ? 0 : hip_fail("aead_seal", e);
 }
 
@@ -1244,14 +1255,9 @@ int qrk_aead_open_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   if (n == 0) return 0;
   if (!keys || !sealed || !sealed_off || !pt || !status || (!aad && (aad_off || aad_len))) return fail("null buffer");
   if (aad_len >> 31) return fail("AEAD row lengths are 32-bit: aad_len must be below 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
-  g_launch_err = hipSuccess;
-  (void)hipGetLastError();
+  CallScope scope;  // not ordered against the context's last use: Open touches no context buffer
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK | CallScope::TIMER)) return -1;
   hipError_t e = aead_open(which, n, keys, sealed, sealed_off, aad, aad_off, aad_len, pt, status, (hipStream_t)stream);
-  if (e == hipSuccess) e = g_launch_err;
   return e == hipSuccess ? 0 : hip_fail("aead_open", e);
 }
 
@@ -1262,12 +1268,14 @@ int qrk_aead_open_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
 extern "C" int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off,
                                       uint8_t* tag, void* stream) {
   if (n && (!key32 || !msg || !msg_off || !tag)) return fail("null buffer");
+  launch_begin();  // no context, so no scope
   hipError_t e = dbg_poly1305(n, key32, msg, msg_off, tag, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("dbg_poly1305", e);
 }
 extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off,
                                    uint8_t* out, void* stream) {
   if (n && (!h || !data || !data_off || !out)) return fail("null buffer");
+  launch_begin();
   hipError_t e = dbg_ghash(n, h, data, data_off, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("dbg_ghash", e);
 }
@@ -1293,30 +1301,23 @@ static int sig_verify(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk
   if (ctx_len > 255) return fail("ML-DSA context strings are at most 255 bytes");
   if (n == 0) return 0;
   if (!pk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  if (ctx_order(ctx, st)) return -1;
-  LastUse last_use{ctx, st};
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
   size_t sz[4];
   mldsa_sizes(which, sz);
   const size_t per_row = mldsa_scratch_bytes(which, 1);
   const size_t cap = std::min({ctx->chunk, (size_t)1 << 20,
                                std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_row / 64 * 64)});
-  const size_t nchunks = (n + cap - 1) / cap;
-  const size_t chunk = std::min(cap, ((n + nchunks - 1) / nchunks + 63) & ~(size_t)63);
+  const size_t chunk = chunk_plan(n, cap);
   if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, mldsa_scratch_bytes(which, chunk), st)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = std::min(chunk, n - off);
     MldsaTrace t = trace;
     if (t.flags) t.mu += off * 64, t.ctilde += off * 64, t.w1 += off * sz[3], t.flags += off;
-    g_launch_err = hipSuccess;
-    (void)hipGetLastError();
+    launch_begin();
     hipError_t e = mldsa_verify(which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str, ctx_len,
                                 status + off, t, ctx->scratch, st);
-    if (e == hipSuccess) e = g_launch_err;
     if (e != hipSuccess) return hip_fail("mldsa_verify", e);
   }
   return 0;
@@ -1346,10 +1347,8 @@ extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t 
 int qrk_base64_encode_batch(qrk_ctx* ctx, size_t n, const uint8_t* in, size_t in_len, uint8_t* out, void* stream) {
   if (!ctx) return fail("null context");
   if (n && in_len && (!in || !out)) return fail("null buffer");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  CallScope scope;
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK | CallScope::TIMER)) return -1;
   hipError_t e = base64_encode(n, in, in_len, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("base64_encode", e);
 }
@@ -1358,10 +1357,8 @@ int qrk_base64_decode_batch(qrk_ctx* ctx, size_t n, const uint8_t* in, size_t ou
                             void* stream) {
   if (!ctx) return fail("null context");
   if (n && out_len && (!in || !out)) return fail("null buffer");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard device_guard;
-  if (device_guard.set(ctx->device)) return -1;
-  TimerScope timer_scope(ctx->profiling ? &ctx->timer : nullptr);
+  CallScope scope;
+  if (scope.open(ctx, (hipStream_t)stream, CallScope::LOCK | CallScope::TIMER)) return -1;
   hipError_t e = hipSuccess;
   if (status && n) e = hipMemsetAsync(status, 0, n * sizeof(int32_t), (hipStream_t)stream);
   if (e == hipSuccess) e = base64_decode(n, in, out_len, out, status, (hipStream_t)stream);

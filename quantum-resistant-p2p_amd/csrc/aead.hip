@@ -492,7 +492,7 @@ hipError_t aead_seal(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* 
   else
     QRK_LAUNCH("k_gcm_seal", st, aead::k_gcm_seal, grid_of(n), dim3(256), 0, st, n, keys, nonces, pt, pt_off, aad,
                aad_off, (uint32_t)aad_len, sealed);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t aead_open(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* sealed, const uint64_t* sealed_off,
@@ -506,21 +506,21 @@ hipError_t aead_open(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* 
   else
     QRK_LAUNCH("k_gcm_open", st, aead::k_gcm_open, grid_of(n), dim3(256), 0, st, n, keys, sealed, sealed_off, aad,
                aad_off, (uint32_t)aad_len, pt, status);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t dbg_poly1305(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off, uint8_t* tag,
                         hipStream_t st) {
   if (n == 0) return hipSuccess;
   QRK_LAUNCH("k_dbg_poly1305", st, aead::k_dbg_poly1305, grid_of(n), dim3(256), 0, st, n, key32, msg, msg_off, tag);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t dbg_ghash(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                      hipStream_t st) {
   if (n == 0) return hipSuccess;
   QRK_LAUNCH("k_dbg_ghash", st, aead::k_dbg_ghash, grid_of(n), dim3(256), 0, st, n, h, data, data_off, out);
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace qrk

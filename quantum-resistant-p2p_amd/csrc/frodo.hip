@@ -1152,7 +1152,7 @@ hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const
   QRK_LAUNCH("k_fr_pack", st, (k_fr_pack<N, 0, fr_npart<N, AES>()>), dim3((unsigned)n), dim3(256), 0, st, n, pk, (size_t)P::PK, v.sp8,
              v.ep16, v.epp16, v.part, v.seeds, mu, (size_t)P::MU, ct, nullptr, nullptr, (size_t)0, v.kk);
   launch_ss<N>(ct, n, v, ss, st);
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int N, bool AES>
@@ -1171,7 +1171,7 @@ hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
              v.sp8, v.ep16, v.epp16, v.part, v.seeds, (const uint8_t*)(v.seeds + 12), (size_t)128, nullptr, ct, sk,
              (size_t)P::SK, v.kk);
   launch_ss<N>(ct, n, v, ss, st);
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int N, bool AES>
@@ -1201,7 +1201,7 @@ hipError_t keypair_t(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, v
     QRK_LAUNCH("k_fr_kg_pkh", st, k_fr_kg_pkh_c<N>, dim3((unsigned)n), dim3(64), 0, st, pk, n, sk);
   else
     QRK_LAUNCH("k_fr_kg_pkh", st, k_fr_kg_pkh<N>, dim3(blocks_for(n)), dim3(256), 0, st, pk, n, sk);
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int N>

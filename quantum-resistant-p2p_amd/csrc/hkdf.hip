@@ -224,14 +224,14 @@ hipError_t hkdf_sha256(size_t n, const uint8_t* ikm, size_t ikm_len, size_t ikm_
   QRK_LAUNCH("k_hkdf_sha256", st, k_hkdf_sha256, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, ikm,
              (uint32_t)ikm_len, ikm_stride, salt, (uint32_t)salt_len, info, info_off, (uint32_t)info_len,
              (uint32_t)L, okm, okm_stride);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t keys_equal(size_t n, const uint8_t* a, const uint8_t* b, size_t len, int32_t* agree, hipStream_t st) {
   if (n == 0) return hipSuccess;
   QRK_LAUNCH("k_keys_equal", st, k_keys_equal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, a, b,
              (uint32_t)len, agree);
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace qrk

@@ -1298,7 +1298,7 @@ hipError_t supports_t(int kind, size_t n, const uint32_t* r, uint32_t* sup, hipS
     QRK_LAUNCH("k_hqc_supports", st, (k_hqc_supports<L, P::W>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, r, sup);
   else
     QRK_LAUNCH("k_hqc_supports", st, (k_hqc_supports<L, P::WR>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, r, sup);
-  return hipGetLastError();
+  return launch_status();
 }
 
 // ---------------------------------------------------------------- launchers
@@ -1358,7 +1358,7 @@ hipError_t keypair_t(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, v
   else
     QRK_LAUNCH("k_hqc_kg_expand", st, k_hqc_kg_expand<L>, dim3(blocks_for(n)), dim3(256), 0, st, coins, n, v.row);
   QRK_LAUNCH("k_hqc_kg_mul", st, k_hqc_kg_mul<L>, dim3((unsigned)n), dim3(HQ<L>::TPB), 0, st, n, v.row, coins, pk, sk);
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int L>
@@ -1371,7 +1371,7 @@ hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const
              pk, ct, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (int32_t*)nullptr,
              v.msg);
   launch_hash<L>(v.msg, n, ss, st);
-  return hipGetLastError();
+  return launch_status();
 }
 
 // m' = C.decode(v - u y): RM symbols -> v.msg (row stride MW * 8), m' -> v.mp (row stride 32)
@@ -1400,7 +1400,7 @@ hipError_t code_decode_t(size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t
   launch_code_decode<L>(n, ct, sk, v, st);
   qrk_chk(hipMemcpy2DAsync(syms, P::N1, v.msg, (size_t)P::MW * 8, P::N1, n, hipMemcpyDeviceToDevice, st));
   qrk_chk(hipMemcpy2DAsync(mprime, P::K, v.mp, 32, P::K, n, hipMemcpyDeviceToDevice, st));
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int L>
@@ -1415,7 +1415,7 @@ hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
   QRK_LAUNCH("k_hqc_enc_mul", st, (k_hqc_enc_mul<L, true>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, v.row,
              (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr, v.mp, sk, ct, stp, v.msg);
   launch_hash<L>(v.msg, n, ss, st);
-  return hipGetLastError();
+  return launch_status();
 }
 
 template <int L>

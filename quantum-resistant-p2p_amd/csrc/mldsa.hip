@@ -314,7 +314,7 @@ static hipError_t run(size_t n, const uint8_t* pk, const uint8_t* msg, const uin
   QRK_LAUNCH("k_mldsa_core", st, k_mldsa_core<PS>, dim3((unsigned)n), dim3(256), 0, st, pk, sig, l.A,
              (const int8_t*)l.c, l.w1, l.flags);
   QRK_LAUNCH("k_mldsa_final", st, k_mldsa_final<PS>, lanes, dim3(64), 0, st, n, sig, l.mu, l.w1, l.flags, status, tr);
-  return hipGetLastError();
+  return launch_status();
 }
 
 static const Params& params_of(int which) { return which == 0 ? P44 : which == 1 ? P65 : P87; }

@@ -2390,17 +2390,17 @@ hipError_t keygen_impl(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
     QRK_LAUNCH("k_keygen_pipe", s.main, k_keygen_pipe<K>, dim3((unsigned)(n * 3 * K)), dim3(64 * (K + 2)), 0, s.main, n,
                coins, pk, sk, (PipeScr*)scratch, s.kg_cnt, n == 1 ? s.done : nullptr, s.ticket, s.kg_err,
                g_kg_dbg_late.load(std::memory_order_relaxed));
-    return hipGetLastError();
+    return launch_status();
   }
   if (n <= QRK_KG_MULTI_MAX && s.kg_cnt) {  // device-pointer calls (no error word), QRK_KG_PIPE=0 builds
     QRK_LAUNCH("k_keygen_multi", s.main, k_keygen_multi<K>, dim3((unsigned)(n * (2 * K + K * K))), dim3(64), 0,
                s.main, n, coins, pk, sk, (MkScr*)scratch, s.kg_cnt, n == 1 ? s.done : nullptr, s.ticket);
-    return hipGetLastError();
+    return launch_status();
   }
   if (n <= QRK_SMALL_MAX) {
     QRK_LAUNCH("k_keygen_one", s.main, k_keygen_one<K>, dim3((unsigned)n), dim3(64 * KG_WAVES), 0, s.main, n, coins,
                pk, sk, n == 1 ? s.done : nullptr, s.ticket);
-    return hipGetLastError();
+    return launch_status();
   }
   hipStream_t st = s.main;
   if (s.xof_keep) v.xof = s.xof_keep;  // the handshake driver keeps A_hat for the same party's Decaps
@@ -2413,7 +2413,7 @@ hipError_t keygen_impl(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
   QRK_LAUNCH("k_keygen_core", st, k_keygen_core<K>, dim3((unsigned)((n + GROUPS - 1) / GROUPS)), dim3(256), 0, st,
              n, C, v.xof, v.prf, pk, sk);
   QRK_LAUNCH("k_back_keygen", st, k_back_keygen<K>, dim3(blocks_for(n)), dim3(256), 0, st, coins, n, pk, sk);
-  return hipGetLastError();
+  return launch_status();
 }
 
 // Encaps: rho copy -> {G(m || H(ek)), SampleNTT} -> {SampleNTT fix-up, PRFs} -> K-PKE.Encrypt
@@ -2428,12 +2428,12 @@ hipError_t encaps_impl(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, co
     if (by_value) memcpy(in.pk, s.host_in1, sizeof(in.pk));
     QRK_LAUNCH("k_encaps_one", s.main, k_encaps_one<K>, dim3((unsigned)n), dim3(64 * ONE_WAVES), 0, s.main, n,
                by_value ? nullptr : pk, coins, in, ct, ss, status, n == 1 ? s.done : nullptr, s.ticket);
-    return hipGetLastError();
+    return launch_status();
   }
   hipStream_t st = s.main;
   poison_xof<K>(C, v, st);
   const RhoSrc rho = rho_source(pk + 384 * K, (size_t)P<K>::PK, n, C, v, s);
-  if (g_launch_err != hipSuccess) return g_launch_err;  // nothing after a failed step
+  if (launch_status() != hipSuccess) return launch_status();  // nothing after a failed step
   const RFrontEnc<K> front{pk, coins, n, ss, v.seeds, blocks_for(n)};
   const RPrf<P<K>::ETA1, P<K>::ETA2> prf{v.seeds, n, C, 2 * K + 1, K, v.prf, blocks_for((2 * K + 1) * C)};
   const RCore<K, 0> core{n, C, v.xof, v.prf, pk, (size_t)P<K>::PK, coins, (size_t)32, ct, status, v.kprime, v.kbar,
@@ -2445,7 +2445,7 @@ hipError_t encaps_impl(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, co
     launch_multi("k_front_encaps+k_xof", {"k_front_encaps", "k_xof"}, s, front, xof_role<K>(rho, n, C, v));
   launch_fix_prf<K>(rho, n, C, v, prf, s);
   launch_one("k_encrypt_core", core, s);
-  return hipGetLastError();
+  return launch_status();
 }
 
 // Decaps: rho copy -> {J(z || c), K-PKE.Decrypt, SampleNTT} -> G(m' || h) -> {SampleNTT fix-up, PRFs}
@@ -2461,7 +2461,7 @@ hipError_t decaps_impl(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* 
     if (by_value) memcpy(in.ct, s.host_in1, sizeof(in.ct));
     QRK_LAUNCH("k_decaps_one", s.main, k_decaps_one<K>, dim3((unsigned)n), dim3(64 * ONE_WAVES), 0, s.main, n,
                by_value ? nullptr : ct, sk, in, ss, n == 1 ? s.done : nullptr, s.ticket);
-    return hipGetLastError();
+    return launch_status();
   }
   hipStream_t st = s.main;
   const unsigned gblocks = (unsigned)((n + GROUPS - 1) / GROUPS);
@@ -2479,11 +2479,11 @@ hipError_t decaps_impl(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* 
       launch_one("k_g_decaps", gd, s);
     launch_one("k_prf", prf, s);
     launch_one("k_encrypt_core", core, s);
-    return hipGetLastError();
+    return launch_status();
   }
   poison_xof<K>(C, v, st);
   const RhoSrc rho = rho_source(sk + 768 * K, (size_t)P<K>::SK, n, C, v, s);
-  if (g_launch_err != hipSuccess) return g_launch_err;  // nothing after a failed step
+  if (launch_status() != hipSuccess) return launch_status();  // nothing after a failed step
   const RCore<K, 1> core{n, C, v.xof, v.prf, sk + 384 * K, (size_t)P<K>::SK, (const uint8_t*)v.mprime, (size_t)32,
                          const_cast<uint8_t*>(ct), nullptr, v.kprime, v.kbar, ss, gblocks};
   // J stays one lane per handshake: at chunks <= 2^15 its launch, {J, decrypt core, SampleNTT}, is
@@ -2499,7 +2499,7 @@ hipError_t decaps_impl(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* 
     launch_one("k_g_decaps", gd, s);
   launch_fix_prf<K>(rho, n, C, v, prf, s);
   launch_one("k_encrypt_core", core, s);
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace mlkem

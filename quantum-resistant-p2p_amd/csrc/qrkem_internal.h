@@ -35,13 +35,27 @@ struct KernelTimer {
 extern thread_local KernelTimer* g_timer;
 // First kernel-launch error of the current library call (HIP resets its last-error state on every
 // later successful API call, so a failed launch followed by successful ones would otherwise go
-// unnoticed); run_batch clears it before each chunk and fails the call when it is set.
+// unnoticed).  The one error channel of the launchers: QRK_LAUNCH and qrk_chk record into it, every
+// launcher returns launch_status(), and only launch_begin() clears it.  An ABI call (abi.cpp: its
+// CallScope, and run_batch / sig_verify before each chunk) calls launch_begin() before it launches.
+// A launcher's return value is therefore the answer and there is no merge step for an entry point
+// to forget; the one thing left to forget is launch_begin(), and that reports an earlier call's
+// failure loudly instead of losing this call's.
 extern thread_local hipError_t g_launch_err;
+// tests only (qrk_dbg_fail_launch): launch_begin() records hipErrorLaunchFailure, as if the call's
+// first launch had been rejected (0 = off).  One relaxed load per launch_begin(), none per launch.
+extern std::atomic<int> g_dbg_fail_launch;
 
 // stream / event / memset calls inside the launchers: a failure joins g_launch_err
 inline void qrk_chk(hipError_t e) {
   if (e != hipSuccess && g_launch_err == hipSuccess) g_launch_err = e;
 }
+inline void launch_begin() {
+  g_launch_err = hipSuccess;
+  (void)hipGetLastError();  // discard HIP's stale error state (e.g. a caller's hipErrorNotReady query)
+  if (g_dbg_fail_launch.load(std::memory_order_relaxed)) qrk_chk(hipErrorLaunchFailure);
+}
+inline hipError_t launch_status() { return g_launch_err; }
 
 #define QRK_LAUNCH(NAME, ST, ...)                   \
   do {                                              \

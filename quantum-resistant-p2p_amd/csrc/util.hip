@@ -33,9 +33,9 @@ __global__ __launch_bounds__(256) void k_bench_coins(size_t n, int nwords, uint6
 hipError_t bench_coins(size_t n, size_t len, uint64_t seed, uint64_t first, uint8_t* out, hipStream_t st) {
   if (len % 8 || len > 136) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bench_coins, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (int)(len / 8), seed,
-                     first, (uint64_t*)out);
-  return hipGetLastError();
+  QRK_LAUNCH("k_bench_coins", st, k_bench_coins, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
+             (int)(len / 8), seed, first, (uint64_t*)out);
+  return launch_status();
 }
 
 // h_i = SHAKE256("qrk-tamper" || LE64(seed) || LE64(i)) first 8 bytes;
@@ -64,8 +64,8 @@ __global__ __launch_bounds__(256) void k_tamper(size_t n, size_t ctlen, uint64_t
 
 hipError_t tamper_ciphertexts(size_t n, size_t ctlen, uint64_t seed, int mode, uint8_t* ct, hipStream_t st) {
   if (n == 0 || mode == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tamper, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, ctlen, seed, mode, ct);
-  return hipGetLastError();
+  QRK_LAUNCH("k_tamper", st, k_tamper, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, ctlen, seed, mode, ct);
+  return launch_status();
 }
 
 // out_i = SHA3-256(a_i || b_i) for n records (a_i = a + i*al, b_i = b + i*bl, bl may be 0):
@@ -122,7 +122,7 @@ hipError_t digest_rows(size_t n, const uint8_t* a, size_t al, const uint8_t* b, 
   if (n == 0) return hipSuccess;
   QRK_LAUNCH("k_digest_rows", st, k_digest_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, a, al, b,
              bl, out);
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace qrk

@@ -248,7 +248,7 @@ hipError_t base64_encode(size_t n, const uint8_t* in, size_t L, uint8_t* out, hi
   const size_t threads = n * ((L + 11) / 12);
   QRK_LAUNCH("k_b64_encode", st, b64::k_b64_encode, dim3(b64::grid(threads)), dim3(256), 0, st, n, in,
              (uint32_t)L, out, (uint32_t)OL);
-  return hipGetLastError();
+  return launch_status();
 }
 
 hipError_t base64_decode(size_t n, const uint8_t* in, size_t L, uint8_t* out, int32_t* status, hipStream_t st) {
@@ -257,7 +257,7 @@ hipError_t base64_decode(size_t n, const uint8_t* in, size_t L, uint8_t* out, in
   const size_t threads = n * ((IL + 15) / 16);
   QRK_LAUNCH("k_b64_decode", st, b64::k_b64_decode, dim3(b64::grid(threads)), dim3(256), 0, st, n, in,
              (uint32_t)IL, out, (uint32_t)L, status);
-  return hipGetLastError();
+  return launch_status();
 }
 
 }  // namespace qrk
