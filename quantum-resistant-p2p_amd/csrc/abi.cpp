@@ -299,6 +299,7 @@ struct CallOpts {
   bool kg_err = false;                // ML-KEM KeyGen: hand the launch the error word, hflag[1]
   uint64_t* xof_keep = nullptr;       // Streams::xof_keep (KeyGen) / xof_given (Decaps): the handshake
   const uint64_t* xof_given = nullptr;  // driver's A_hat hand-over
+  uint8_t* frodo_mu = nullptr;        // FrodoKEM Decaps (tests): mu' [n][32], copied out before each chunk's cleanse
 };
 
 // FrodoKEM scratch is 0.14-0.53 MB per handshake, HQC's 9-24 KB: their chunks are capped so
@@ -483,6 +484,7 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
       case Op::DECAPS:
         if (stat && !f.decaps_sets_status) e = hipMemsetAsync(stat, 0, m * sizeof(int32_t), st);
         if (e == hipSuccess) e = f.decaps(a, m, o1 + off * a.ss, i1 + off * a.ct, i2 + off * a.sk, stat, ctx->scratch, S);
+        if (e == hipSuccess && opts.frodo_mu) e = frodo_trace_mu(a, m, ctx->scratch, opts.frodo_mu + off * 32, st);
         break;
     }
     HT(4);
@@ -1342,6 +1344,24 @@ extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t 
   MldsaTrace t;
   t.mu = mu, t.ctilde = ctilde, t.w1 = w1, t.flags = flags;
   return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
+}
+
+// Tests only (not in qrkem.h): qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes, per
+// row, mu' = Decode(C - B'S) to mu_out [n][32] (len_mu = 16 / 24 / 32 bytes, then zeros).  The launches
+// are those of the public call; mu' is read from the scratch record k_fr_dec_m wrote (seeds[12..]) before
+// each chunk's cleanse.  On a ciphertext that fails the re-encryption check ss = H(ct || s) whatever
+// Decode returned, so this is the only place a wrong mu' on such a row shows.
+extern "C" int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
+                                          const uint8_t* sk, uint8_t* mu_out, void* stream) {
+  if (!ctx) return fail("null context");
+  const AlgInfo* a = resolve(alg);
+  if (!a) return -1;
+  if (a->family != Family::FRODO) return fail(std::string("not a FrodoKEM parameter set: ") + alg);
+  if (n && (!ss || !ct || !sk || !mu_out)) return fail("null buffer");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallOpts opts;
+  opts.frodo_mu = mu_out;
+  return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, (hipStream_t)stream, opts);
 }
 
 int qrk_base64_encode_batch(qrk_ctx* ctx, size_t n, const uint8_t* in, size_t in_len, uint8_t* out, void* stream) {

@@ -1211,7 +1211,36 @@ hipError_t cleanse_t(size_t n, void* scratch, hipStream_t st) {
   return hipMemsetAsync(v.seeds, 0, (size_t)((uint8_t*)v.aesp - (uint8_t*)v.seeds), st);  // seeds | kk
 }
 
+// Tests only (qrk_dbg_frodo_decaps_trace): mu' of each handshake, as k_fr_dec_m left it in
+// seeds[hs * 16 + 12 ..], to out[hs][32] (MU bytes, then zeros).  One thread per output byte.
+template <int N>
+__global__ __launch_bounds__(256) void k_fr_dbg_mu(size_t n, const uint64_t* __restrict__ seeds,
+                                                   uint8_t* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t hs = t >> 5;
+  const int b = (int)(t & 31);
+  if (hs >= n) return;
+  out[t] = b < FP<N>::MU ? ((const uint8_t*)(seeds + hs * 16 + 12))[b] : (uint8_t)0;
+}
+
+template <int N>
+hipError_t trace_mu_t(size_t n, void* scratch, uint8_t* out, hipStream_t st) {
+  const View<N> v = carve<N>(scratch, round64(n));
+  QRK_LAUNCH("k_fr_dbg_mu", st, k_fr_dbg_mu<N>, dim3(blocks_for(n * 32)), dim3(256), 0, st, n, v.seeds, out);
+  return launch_status();
+}
+
 }  // namespace frodo
+
+hipError_t frodo_trace_mu(const AlgInfo& a, size_t n, void* scratch, uint8_t* mu_out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  switch (a.k) {
+    case 640: return frodo::trace_mu_t<640>(n, scratch, mu_out, st);
+    case 976: return frodo::trace_mu_t<976>(n, scratch, mu_out, st);
+    case 1344: return frodo::trace_mu_t<1344>(n, scratch, mu_out, st);
+  }
+  return hipErrorInvalidValue;
+}
 
 hipError_t frodo_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st) {
   if (n == 0) return hipSuccess;

@@ -156,6 +156,10 @@ hipError_t frodo_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, co
 hipError_t frodo_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
                         int32_t* status, void* scratch, const Streams& st);
 
+// tests only (qrk_dbg_frodo_decaps_trace): after frodo_decaps on the same chunk and scratch and before
+// frodo_cleanse, mu' = Decode(C - B'S) of each handshake to mu_out[n][32] (len_mu bytes, then zeros)
+hipError_t frodo_trace_mu(const AlgInfo& a, size_t n, void* scratch, uint8_t* mu_out, hipStream_t st);
+
 hipError_t hqc_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
                        const Streams& st);
 hipError_t hqc_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* coins,

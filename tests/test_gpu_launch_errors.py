@@ -230,6 +230,16 @@ def sig_verify(lib, ctx):
                                             sig.data_ptr(), None, 0, st.data_ptr(), _stream()), [st]
 
 
+def frodo_decaps_trace(lib, ctx):
+    alg, n = "FrodoKEM-640-SHAKE", 64
+    s, _, _, _, sk, c = _kem_chain(lib, ctx, alg, n)
+    lib.qrk_dbg_frodo_decaps_trace.restype = ct.c_int
+    lib.qrk_dbg_frodo_decaps_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P]
+    ss, mu = _out(n, s["ss"]), _out(n, 32)
+    return lambda: lib.qrk_dbg_frodo_decaps_trace(ctx, alg.encode(), n, ss.data_ptr(), c.data_ptr(), sk.data_ptr(),
+                                                  mu.data_ptr(), _stream()), [ss, mu]
+
+
 def dbg_hook(name, fixed_len):
     def build(lib, ctx):
         n = 64
@@ -248,6 +258,7 @@ CASES.update({
     "base64_decode": base64_decode, "hqc_supports": hqc_supports, "hqc_code_decode": hqc_code_decode,
     "bench_coins": bench_coins, "tamper": tamper, "sig_verify-ML-DSA-44": sig_verify,
     "dbg_poly1305": dbg_hook("qrk_dbg_poly1305_batch", 32), "dbg_ghash": dbg_hook("qrk_dbg_ghash_batch", 16),
+    "dbg_frodo_decaps_trace-FrodoKEM-640-SHAKE-64": frodo_decaps_trace,
 })
 for _alg in ("AES-256-GCM", "ChaCha20-Poly1305"):
     CASES[f"aead_seal-{_alg}"] = aead_seal(_alg)
