@@ -201,6 +201,14 @@ int qrk_hqc_supports(qrk_ctx *ctx, const char *alg, int kind, size_t n, const ui
  * chunk for the algorithm (qrk_ctx_effective_chunk). */
 int qrk_hqc_code_decode(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *ct,
                         uint8_t *syms, uint8_t *mprime, void *stream);
+/* TEST HOOK, not for applications: qrk_hqc_code_decode (same contract, same limit on n) that also
+ * returns the word the decoder is given.  t_out [n][n1 n2 / 8]: the n1 n2 bits of v - u y exactly as
+ * the kernel hands them to the Reed-Muller stage, little-endian bytes as in the ciphertext's v.  The
+ * sparse-dense product u y is otherwise visible only through a decoder that absorbs dozens of wrong
+ * bits per block; stored by the production kernel's own code under a compile-time switch that is off
+ * in every other call. */
+int qrk_dbg_hqc_decaps_trace(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *ct,
+                             uint8_t *t_out, uint8_t *syms, uint8_t *mprime, void *stream);
 
 /* HKDF-SHA256 (RFC 5869) over n keys, one GPU lane per key.  Replaces
  * SecureMessaging._derive_symmetric_key (messaging.py:350-382: HKDF(SHA256,

@@ -1118,23 +1118,36 @@ int qrk_hqc_supports(qrk_ctx* ctx, const char* alg, int kind, size_t n, const ui
   return e == hipSuccess ? 0 : hip_fail("hqc_supports", e);
 }
 
-int qrk_hqc_code_decode(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
-                        uint8_t* mprime, void* stream) {
+// qrk_hqc_code_decode and its traced twin qrk_dbg_hqc_decaps_trace (t_out != NULL): one body, so the
+// chunk limit, the argument checks and the failed-launch reporting are the same
+static int hqc_code_decode_call(const char* what, qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk,
+                                const uint8_t* ct, uint8_t* t_out, bool traced, uint8_t* syms, uint8_t* mprime,
+                                void* stream) {
   if (!ctx) return fail("null context");
   const AlgInfo* a = resolve(alg);
   if (!a) return -1;
   if (a->family != Family::HQC) return fail(std::string("not an HQC parameter set: ") + alg);
   if (n == 0) return 0;
-  if (!sk || !ct || !syms || !mprime) return fail("null buffer");
+  if (!sk || !ct || !syms || !mprime || (traced && !t_out)) return fail("null buffer");
   hipStream_t st = (hipStream_t)stream;
   CallScope scope;
   if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
-  if (n > chunk_for(ctx, *a)) return fail("hqc_code_decode: n exceeds the context chunk");
+  if (n > chunk_for(ctx, *a)) return fail(std::string(what) + ": n exceeds the context chunk");
   if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, ops_of(*a).scratch_bytes(*a, round64(n)), st)) return -1;
-  hipError_t e = hqc_code_decode(*a, n, sk, ct, syms, mprime, ctx->scratch, st);
-  if (e != hipSuccess) return hip_fail("hqc_code_decode", e);
+  hipError_t e = hqc_code_decode(*a, n, sk, ct, t_out, syms, mprime, ctx->scratch, st);
+  if (e != hipSuccess) return hip_fail(what, e);
   e = ops_of(*a).cleanse(*a, n, ctx->scratch, st);  // the symbols and m' do not outlive the call
   return e == hipSuccess ? 0 : hip_fail("hipMemsetAsync(cleanse)", e);
+}
+
+int qrk_hqc_code_decode(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
+                        uint8_t* mprime, void* stream) {
+  return hqc_code_decode_call("hqc_code_decode", ctx, alg, n, sk, ct, nullptr, false, syms, mprime, stream);
+}
+
+int qrk_dbg_hqc_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct,
+                             uint8_t* t_out, uint8_t* syms, uint8_t* mprime, void* stream) {
+  return hqc_code_decode_call("hqc_decaps_trace", ctx, alg, n, sk, ct, t_out, true, syms, mprime, stream);
 }
 
 int qrk_hkdf_sha256_batch(qrk_ctx* ctx, size_t n, const uint8_t* ikm, size_t ikm_len, const uint8_t* salt,

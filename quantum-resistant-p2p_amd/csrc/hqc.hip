@@ -441,10 +441,11 @@ __global__ __launch_bounds__(64) void k_hqc_hash_c(const uint64_t* __restrict__ 
 
 // ---------------------------------------------------------------- workgroup / hs helpers
 // Thread index as seen by the workgroup helpers: threadIdx.x plus an opaque zero produced inside
-// the caller's code (a volatile v_mov).  In the persistent handshake loop (k_hqc_enc_mul) the
-// compiler would otherwise hoist every loop-invariant LDS address out of the loop and keep it
-// live in a register (110-180 VGPRs, then spills under an occupancy bound); derived from this
-// value, the addresses are recomputed per iteration (a few VALU ops) instead.
+// the caller's code (a volatile v_mov).  k_hqc_enc_mul is launched with one workgroup per
+// handshake (grid = n), but keeps the shape of a handshake loop whose body runs once; around it the
+// compiler would otherwise hoist every loop-invariant LDS address and keep it live in a register
+// (110-180 VGPRs, then spills under an occupancy bound); derived from this value, the addresses are
+// recomputed where they are used (a few VALU ops) instead.
 __device__ __forceinline__ int hq_tid() {
   int z;
   asm volatile("v_mov_b32 %0, 0" : "=v"(z));
@@ -1058,11 +1059,13 @@ __device__ __forceinline__ uint32_t max_wave(uint32_t k) {
 
 // ---------------------------------------------------------------- Decaps: m' = C.decode(v - u y)
 // The combined product T reuses the u || v staging buffer (v is folded into the partial sums before
-// the combine): one barrier more and NWP words less LDS per workgroup
-template <int L>
+// the combine): one barrier more and NWP words less LDS per workgroup.
+// TRACE (tests only, qrk_dbg_hqc_decaps_trace): the n1 n2 bits of T also go to t_out [n][VB], as the
+// RM stage reads them; production launches TRACE = false, where t_out is never touched.
+template <int L, bool TRACE>
 __global__ __launch_bounds__(HQ<L>::TPB) __attribute__((amdgpu_waves_per_eu(L == 192 ? 8 : 1))) void k_hqc_decode(size_t n, const uint64_t* __restrict__ row,
                                                     const uint8_t* __restrict__ ct, uint8_t* __restrict__ syms,
-                                                    size_t sym_stride) {
+                                                    size_t sym_stride, uint8_t* __restrict__ t_out) {
   using P = HQ<L>;
   __shared__ uint32_t D1[P::NH2];
   constexpr int MBD = (P::NB + P::VB + 8) / 4 + 1;
@@ -1110,6 +1113,10 @@ __global__ __launch_bounds__(HQ<L>::TPB) __attribute__((amdgpu_waves_per_eu(L ==
   uint32_t* const outs[1] = {T};
   prod_combine<1, P::WPT, P::NBT>(outs, acc, [] {});
   HQ_MARK(20);
+  if constexpr (TRACE) {
+    uint8_t* to = t_out + hs * P::VB;
+    for (int b = t; b < P::VB; b += P::TPB) to[b] = mb[b];  // T is only read from here on
+  }
   // duplicated RM(1,7): one wave per symbol pair (two independent chains interleave), lane l
   // holds positions l and l + 64 of each symbol; the Hadamard butterflies exchange through DPP
   // and v_permlane16/32_swap (no LDS round trips), the first maximum is a DPP + readlane max
@@ -1376,7 +1383,8 @@ hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const
 
 // m' = C.decode(v - u y): RM symbols -> v.msg (row stride MW * 8), m' -> v.mp (row stride 32)
 template <int L>
-void launch_code_decode(size_t n, const uint8_t* ct, const uint8_t* sk, const View& v, hipStream_t st) {
+void launch_code_decode(size_t n, const uint8_t* ct, const uint8_t* sk, const View& v, hipStream_t st,
+                        uint8_t* t_out = nullptr) {
   using P = HQ<L>;
   if (n <= QRK_HQC_COOP_MAX)
     QRK_LAUNCH("k_hqc_dec_expand", st, k_hqc_dec_expand_c<L>, dim3((unsigned)n), dim3(64), 0, st, sk, n, v.row);
@@ -1384,20 +1392,24 @@ void launch_code_decode(size_t n, const uint8_t* ct, const uint8_t* sk, const Vi
     QRK_LAUNCH("k_hqc_dec_expand", st, k_hqc_dec_expand<L>, dim3(blocks_for(n)), dim3(256), 0, st, sk, n, v.row);
   // the RM stage's symbols go through the K-hash message area, which is free until the re-encryption
   uint8_t* syms = (uint8_t*)v.msg;
-  QRK_LAUNCH("k_hqc_decode", st, k_hqc_decode<L>, dim3((unsigned)n), dim3(P::TPB), 0, st, n, v.row, ct, syms,
-             (size_t)P::MW * 8);
+  if (t_out)
+    QRK_LAUNCH("k_hqc_decode", st, (k_hqc_decode<L, true>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, v.row, ct, syms,
+               (size_t)P::MW * 8, t_out);
+  else
+    QRK_LAUNCH("k_hqc_decode", st, (k_hqc_decode<L, false>), dim3((unsigned)n), dim3(P::TPB), 0, st, n, v.row, ct, syms,
+               (size_t)P::MW * 8, (uint8_t*)nullptr);
   QRK_LAUNCH("k_hqc_rs", st, k_hqc_rs<L>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, (const uint8_t*)syms,
              (size_t)P::MW * 8, v.mp);
 }
 
-// (test hook behind qrk_hqc_code_decode: the decoder stages of Decaps alone, their scratch rows
-// copied out dense)
+// (test hook behind qrk_hqc_code_decode and qrk_dbg_hqc_decaps_trace: the decoder stages of Decaps
+// alone, their scratch rows copied out dense; with t_out, k_hqc_decode also stores T = v - u y there)
 template <int L>
-hipError_t code_decode_t(size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms, uint8_t* mprime, void* scratch,
-                         hipStream_t st) {
+hipError_t code_decode_t(size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* t_out, uint8_t* syms, uint8_t* mprime,
+                         void* scratch, hipStream_t st) {
   using P = HQ<L>;
   View v = carve<L>(scratch, n);
-  launch_code_decode<L>(n, ct, sk, v, st);
+  launch_code_decode<L>(n, ct, sk, v, st, t_out);
   qrk_chk(hipMemcpy2DAsync(syms, P::N1, v.msg, (size_t)P::MW * 8, P::N1, n, hipMemcpyDeviceToDevice, st));
   qrk_chk(hipMemcpy2DAsync(mprime, P::K, v.mp, 32, P::K, n, hipMemcpyDeviceToDevice, st));
   return launch_status();
@@ -1476,13 +1488,13 @@ hipError_t hqc_supports(const AlgInfo& a, int kind, size_t n, const uint32_t* r,
   return hipErrorInvalidValue;
 }
 
-hipError_t hqc_code_decode(const AlgInfo& a, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
-                           uint8_t* mprime, void* scratch, hipStream_t st) {
+hipError_t hqc_code_decode(const AlgInfo& a, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* t_out,
+                           uint8_t* syms, uint8_t* mprime, void* scratch, hipStream_t st) {
   if (n == 0) return hipSuccess;
   switch (a.k) {
-    case 128: return hqc::code_decode_t<128>(n, sk, ct, syms, mprime, scratch, st);
-    case 192: return hqc::code_decode_t<192>(n, sk, ct, syms, mprime, scratch, st);
-    case 256: return hqc::code_decode_t<256>(n, sk, ct, syms, mprime, scratch, st);
+    case 128: return hqc::code_decode_t<128>(n, sk, ct, t_out, syms, mprime, scratch, st);
+    case 192: return hqc::code_decode_t<192>(n, sk, ct, t_out, syms, mprime, scratch, st);
+    case 256: return hqc::code_decode_t<256>(n, sk, ct, t_out, syms, mprime, scratch, st);
   }
   return hipErrorInvalidValue;
 }

@@ -170,9 +170,10 @@ hipError_t hqc_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct
 // 1: w = the encryption weight w_r = w_e): sup_i = i + floor(r_i (n - i) / 2^32), deduplicated.
 hipError_t hqc_supports(const AlgInfo& a, int kind, size_t n, const uint32_t* r, uint32_t* sup, hipStream_t st);
 // The decoder stages of Decaps alone (dec_expand, RM decode, RS decode) on `scratch`: the RM
-// symbols syms[n][n1] and the decoded message mprime[n][k], dense.
-hipError_t hqc_code_decode(const AlgInfo& a, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* syms,
-                           uint8_t* mprime, void* scratch, hipStream_t st);
+// symbols syms[n][n1] and the decoded message mprime[n][k], dense.  With t_out (tests only,
+// qrk_dbg_hqc_decaps_trace; else NULL) k_hqc_decode also stores T = v - u y to t_out[n][VB].
+hipError_t hqc_code_decode(const AlgInfo& a, size_t n, const uint8_t* sk, const uint8_t* ct, uint8_t* t_out,
+                           uint8_t* syms, uint8_t* mprime, void* scratch, hipStream_t st);
 
 // SHAKE256("qrk-bench" || LE64(seed) || LE64(first + i), len) for i < n, len <= 136.
 hipError_t bench_coins(size_t n, size_t len, uint64_t seed, uint64_t first, uint8_t* out, hipStream_t st);

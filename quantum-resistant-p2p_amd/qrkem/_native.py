@@ -60,6 +60,7 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_digest_rows": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P]),
         "qrk_hqc_supports": (ct.c_int, [P, ct.c_char_p, ct.c_int, SZ, P, P, P]),
         "qrk_hqc_code_decode": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P]),
+        "qrk_dbg_hqc_decaps_trace": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, P]),
         "qrk_hkdf_sha256_batch": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P, SZ, P, SZ, P]),
         "qrk_handshake_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, SZ, P, P, P, P, P, P, P]),
         "qrk_aead_seal_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, P, SZ, P, P]),

@@ -272,3 +272,19 @@ class BatchKEM:
         self._check(LIB.qrk_hqc_code_decode(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(syms), _dptr(mp),
                                             self._stream()), "hqc_code_decode")
         return syms, mp
+
+    def hqc_decaps_trace(self, sk, ct_):
+        """hqc_code_decode plus the word the decoder is given: returns (t [n, n1 n2 / 8], the bits of
+        v - u y as k_hqc_decode hands them to the Reed-Muller stage; syms; mprime) (test hook,
+        qrk_dbg_hqc_decaps_trace).  Outputs are pre-filled with 0xA5 so a missing store shows."""
+        if not self.alg.startswith("HQC-"):
+            raise ValueError(f"not an HQC parameter set: {self.alg}")
+        n = _check_dev(sk, self.sk_len, "decaps_trace sk").shape[0]
+        _check_dev(ct_, self.ct_len, "decaps_trace ct", n)
+        k = self.enc_coins - 16
+        n1 = {16: 46, 24: 56, 32: 90}[k]
+        vb = self.ct_len - 16 - (self.pk_len - 40)
+        t, syms, mp = (self._empty(n, w).fill_(0xA5) for w in (vb, n1, k))
+        self._check(LIB.qrk_dbg_hqc_decaps_trace(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(t), _dptr(syms),
+                                                 _dptr(mp), self._stream()), "hqc_decaps_trace")
+        return t, syms, mp

@@ -6,7 +6,9 @@ restatement and the frozen vectors in tests/test_hqc_oracle.py.  PARITY UNPINNED
 liboqs itself (no HQC KATs offline).  Sizes are ragged; the chunked path is covered.
 Every accepted ciphertext here is an honest one (the decoder corrects next to nothing);
 tests/test_gpu_hqc_decoder.py holds the RM / Reed-Solomon decoder to the spec at and beyond
-its correction radius.
+its correction radius.  Every operand here is pseudo-random; tests/test_gpu_hqc_product.py holds
+the sparse x dense ring products to the spec at the edges of support and operand (position 0
+and n - 1, the last operand word, stray bits above X^(n-1)) and reads Decaps' v - u y itself.
 """
 import hashlib
 import json

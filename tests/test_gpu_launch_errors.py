@@ -185,6 +185,15 @@ def hqc_code_decode(lib, ctx):
                                            mp.data_ptr(), _stream()), [syms, mp]
 
 
+def hqc_decaps_trace(lib, ctx):
+    import hqc_spec as H
+    n, p = 64, H.params("HQC-128")
+    _, _, _, _, sk, c = _kem_chain(lib, ctx, "HQC-128", n)
+    t, syms, mp = _out(n, p["vb"]), _out(n, p["n1"]), _out(n, p["k"])
+    return lambda: lib.qrk_dbg_hqc_decaps_trace(ctx, b"HQC-128", n, sk.data_ptr(), c.data_ptr(), t.data_ptr(),
+                                                syms.data_ptr(), mp.data_ptr(), _stream()), [t, syms, mp]
+
+
 def bench_coins(lib, ctx):
     n, out = 64, _out(64, 96)
     return lambda: lib.qrk_bench_coins(ctx, n, 96, 0x5EED, 7, out.data_ptr(), _stream()), [out]
@@ -256,6 +265,7 @@ CASES.update({f"{op}-host-ML-KEM-512-1": kem_host("ML-KEM-512", op) for op in ("
 CASES.update({
     "handshake-ML-KEM-512-64": handshake, "hkdf": hkdf, "digest_rows": digest_rows, "base64_encode": base64_encode,
     "base64_decode": base64_decode, "hqc_supports": hqc_supports, "hqc_code_decode": hqc_code_decode,
+    "dbg_hqc_decaps_trace": hqc_decaps_trace,
     "bench_coins": bench_coins, "tamper": tamper, "sig_verify-ML-DSA-44": sig_verify,
     "dbg_poly1305": dbg_hook("qrk_dbg_poly1305_batch", 32), "dbg_ghash": dbg_hook("qrk_dbg_ghash_batch", 16),
     "dbg_frodo_decaps_trace-FrodoKEM-640-SHAKE-64": frodo_decaps_trace,
