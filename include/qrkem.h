@@ -272,6 +272,13 @@ int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
  * 1174, 1480).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; any other name returns -1 with
  * qrk_last_error() set.  Verification only: there is no KeyGen or Sign (the OQS_SIG registry of
  * Part 1 stays empty).
+ * The same two calls verify hash-based signatures, the SHA2 "f" parameter sets, in two flavours:
+ * "SPHINCS+-SHA2-128f-simple", "SPHINCS+-SHA2-192f-simple", "SPHINCS+-SHA2-256f-simple" (the round-3.1
+ * submission as liboqs ships it, what the reference's SPHINCSSignature asks for, signatures.py:208-212)
+ * and "SLH-DSA-SHA2-128f", "SLH-DSA-SHA2-192f", "SLH-DSA-SHA2-256f" (FIPS 205 pure SLH-DSA, Algorithm 24).
+ * The flavours differ in the message framing (FIPS 205: 0 || len(ctx) || ctx || M; round 3.1: M) and in
+ * the bit order of the FORS indices, and do not verify each other's signatures.  Parity with liboqs and
+ * the FIPS 205 KATs is unpinned, as for ML-DSA.
  * out[0..2] = public key, secret key, signature bytes; -1 for an unknown name. */
 int qrk_sig_sizes(const char *alg, size_t out[3]);
 /* n verifications.  Device pointers: pk [n][pk bytes], sig [n][sig bytes], messages ragged (bytes +
@@ -279,7 +286,10 @@ int qrk_sig_sizes(const char *alg, size_t out[3]);
  * empty, what liboqs's OQS_SIG_sign uses; ctx_len > 255 returns -1).
  * status (required, int32[n]): 0 valid, -1 otherwise; every row is written exactly once.  A row of
  * 2^31 bytes or more gets -1.  Stream-ordered on `stream`; uses the context's scratch (k l KiB + about
- * 1.3 KB per row, grown on demand; qrk_ctx_set_chunk bounds the rows per launch). */
+ * 1.3 KB per row, grown on demand; qrk_ctx_set_chunk bounds the rows per launch).
+ * SLH-DSA / SPHINCS+ names: the same contract; the scratch is the H_msg digest and a flag word per row
+ * (38 / 46 / 53 bytes).  A context string exists only under the "SLH-DSA-" names (ctx_len > 255 returns
+ * -1); under a "SPHINCS+-" name any ctx_len != 0 returns -1 before any device work. */
 int qrk_sig_verify_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *pk, const uint8_t *msg,
                          const uint64_t *msg_off, const uint8_t *sig, const uint8_t *ctx_str, size_t ctx_len,
                          int32_t *status, void *stream);

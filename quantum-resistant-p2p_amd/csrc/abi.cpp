@@ -1295,45 +1295,94 @@ extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* da
   return e == hipSuccess ? 0 : hip_fail("dbg_ghash", e);
 }
 
-// ------------------------------------------------------------------ ML-DSA verification (mldsa.hip)
+// ------------------------------------------------------------------ signature verification (mldsa.hip, slhdsa.hip)
+// One family lookup for both entry points: ML-DSA first, then SLH-DSA / SPHINCS+.
+enum class SigFamily { NONE, MLDSA, SLHDSA };
+struct SigAlg {
+  SigFamily family = SigFamily::NONE;
+  int which = -1;
+};
+static SigAlg sig_find(const char* alg) {
+  SigAlg a;
+  if ((a.which = mldsa_find(alg)) >= 0)
+    a.family = SigFamily::MLDSA;
+  else if ((a.which = slhdsa_find(alg)) >= 0)
+    a.family = SigFamily::SLHDSA;
+  return a;
+}
+static int sig_unsupported(const char* alg) {
+  return fail(std::string("unsupported signature algorithm: ") + (alg ? alg : "(null)"));
+}
+
 int qrk_sig_sizes(const char* alg, size_t out[3]) {
-  const int which = mldsa_find(alg);
-  if (which < 0 || !out) return fail(std::string("unsupported signature algorithm: ") + (alg ? alg : "(null)"));
-  size_t s[4];
-  mldsa_sizes(which, s);
+  const SigAlg a = sig_find(alg);
+  if (a.family == SigFamily::NONE || !out) return sig_unsupported(alg);
+  size_t s[6];
+  if (a.family == SigFamily::MLDSA)
+    mldsa_sizes(a.which, s);
+  else
+    slhdsa_sizes(a.which, s);
   out[0] = s[0], out[1] = s[1], out[2] = s[2];
   return 0;
 }
 
-// The scratch is k l KiB + about 1.3 KB per row (A_hat, mu, w1, c, flags): chunks are capped like the
-// families' (chunk_for) and run as equal multiples of 64 with a shorter tail.
+// The traces of the two families' test hooks; `family` says which hook is calling (NONE: the public call).
+struct SigTrace {
+  SigFamily family = SigFamily::NONE;
+  MldsaTrace mldsa;
+  SlhdsaTrace slhdsa;
+};
+
+// ML-DSA's scratch is k l KiB + about 1.3 KB per row (A_hat, mu, w1, c, flags), SLH-DSA's the digest and a
+// flag word (38 to 53 bytes): chunks are capped like the families' (chunk_for) and run as equal multiples
+// of 64 with a shorter tail.
 static int sig_verify(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
                       const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
-                      int32_t* status, const MldsaTrace& trace, void* stream) {
+                      int32_t* status, const SigTrace& trace, void* stream) {
   if (!ctx) return fail("null context");
-  const int which = mldsa_find(alg);
-  if (which < 0) return fail(std::string("unsupported signature algorithm: ") + (alg ? alg : "(null)"));
-  if (ctx_len > 255) return fail("ML-DSA context strings are at most 255 bytes");
+  const SigAlg a = sig_find(alg);
+  if (a.family == SigFamily::NONE || (trace.family != SigFamily::NONE && trace.family != a.family))
+    return sig_unsupported(alg);
+  const bool dsa = a.family == SigFamily::MLDSA;
+  if (ctx_len > 255) return fail(dsa ? "ML-DSA context strings are at most 255 bytes"
+                                     : "SLH-DSA context strings are at most 255 bytes");
+  if (!dsa && ctx_len && !slhdsa_is_fips(a.which))
+    return fail(std::string(alg) + " is the round-3.1 submission, which has no context string (ctx_len must be 0; "
+                                   "the SLH-DSA-SHA2-* names take one)");
   if (n == 0) return 0;
   if (!pk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
   hipStream_t st = (hipStream_t)stream;
   CallScope scope;
   if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
-  size_t sz[4];
-  mldsa_sizes(which, sz);
-  const size_t per_row = mldsa_scratch_bytes(which, 1);
+  size_t sz[6];
+  if (dsa)
+    mldsa_sizes(a.which, sz);
+  else
+    slhdsa_sizes(a.which, sz);
+  auto scratch_bytes = [&](size_t rows) {
+    return dsa ? mldsa_scratch_bytes(a.which, rows) : slhdsa_scratch_bytes(a.which, rows);
+  };
+  const size_t per_row = scratch_bytes(1);
   const size_t cap = std::min({ctx->chunk, (size_t)1 << 20,
                                std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_row / 64 * 64)});
   const size_t chunk = chunk_plan(n, cap);
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, mldsa_scratch_bytes(which, chunk), st)) return -1;
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_bytes(chunk), st)) return -1;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = std::min(chunk, n - off);
-    MldsaTrace t = trace;
-    if (t.flags) t.mu += off * 64, t.ctilde += off * 64, t.w1 += off * sz[3], t.flags += off;
     launch_begin();
-    hipError_t e = mldsa_verify(which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str, ctx_len,
-                                status + off, t, ctx->scratch, st);
-    if (e != hipSuccess) return hip_fail("mldsa_verify", e);
+    if (dsa) {
+      MldsaTrace t = trace.mldsa;
+      if (t.flags) t.mu += off * 64, t.ctilde += off * 64, t.w1 += off * sz[3], t.flags += off;
+      hipError_t e = mldsa_verify(a.which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str,
+                                  ctx_len, status + off, t, ctx->scratch, st);
+      if (e != hipSuccess) return hip_fail("mldsa_verify", e);
+    } else {
+      SlhdsaTrace t = trace.slhdsa;
+      if (t.flags) t.digest += off * sz[3], t.fors_pk += off * sz[4], t.roots += off * sz[5] * sz[4], t.flags += off;
+      hipError_t e = slhdsa_verify(a.which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str,
+                                   ctx_len, status + off, t, ctx->scratch, st);
+      if (e != hipSuccess) return hip_fail("slhdsa_verify", e);
+    }
   }
   return 0;
 }
@@ -1341,7 +1390,7 @@ static int sig_verify(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk
 int qrk_sig_verify_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
                          const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
                          int32_t* status, void* stream) {
-  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, MldsaTrace{}, stream);
+  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, SigTrace{}, stream);
 }
 
 // Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed
@@ -1354,8 +1403,25 @@ extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t 
                                           const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
                                           uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream) {
   if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
-  MldsaTrace t;
-  t.mu = mu, t.ctilde = ctilde, t.w1 = w1, t.flags = flags;
+  SigTrace t;
+  t.family = SigFamily::MLDSA;
+  t.mldsa.mu = mu, t.mldsa.ctilde = ctilde, t.mldsa.w1 = w1, t.mldsa.flags = flags;
+  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
+}
+
+// Tests only (not in qrkem.h): qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name that also writes, per row,
+// the H_msg digest [n][m], the FORS public key [n][n], the root every hypertree layer reconstructed
+// [n][d][n] and a flag word (bit 0: the top root differs from PK.root; bit 1, internal: a row of 2^31
+// bytes or more, whose other three outputs are zeros).  The production kernel stores them itself, in an
+// instantiation no other call launches; parity with tests/slhdsa_spec.py is byte-level per layer.
+extern "C" int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk,
+                                           const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
+                                           const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* digest,
+                                           uint8_t* fors_pk, uint8_t* roots, uint32_t* flags, void* stream) {
+  if (n && (!digest || !fors_pk || !roots || !flags)) return fail("null trace buffer");
+  SigTrace t;
+  t.family = SigFamily::SLHDSA;
+  t.slhdsa.digest = digest, t.slhdsa.fors_pk = fors_pk, t.slhdsa.roots = roots, t.slhdsa.flags = flags;
   return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
 }
 

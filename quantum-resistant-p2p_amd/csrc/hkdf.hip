@@ -15,93 +15,10 @@
 // (its info bytes are gathered with byte loads because every key's info has its own
 // length and offset).
 #include "qrkem_internal.h"
+#include "sha2.cuh"
 
 namespace qrk {
 namespace sha {
-
-struct K256T {
-  uint32_t k[64];
-};
-constexpr K256T K256 = {{
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u}};
-
-struct H8 {
-  uint32_t h[8];
-};
-__device__ __forceinline__ H8 init() {
-  return H8{{0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu,
-             0x5be0cd19u}};
-}
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
-
-// One SHA-256 compression of the 16 big-endian words w into s.
-__device__ __forceinline__ void compress(H8& s, const uint32_t win[16]) {
-  uint32_t w[16];
-#pragma unroll
-  for (int t = 0; t < 16; ++t) w[t] = win[t];
-  uint32_t a = s.h[0], b = s.h[1], c = s.h[2], d = s.h[3], e = s.h[4], f = s.h[5], g = s.h[6], h = s.h[7];
-#pragma unroll
-  for (int t = 0; t < 64; ++t) {
-    if (t >= 16) {
-      const uint32_t x = w[(t + 1) & 15], y = w[(t + 14) & 15];
-      const uint32_t s0 = rotr(x, 7) ^ rotr(x, 18) ^ (x >> 3);
-      const uint32_t s1 = rotr(y, 17) ^ rotr(y, 19) ^ (y >> 10);
-      w[t & 15] += s0 + w[(t + 9) & 15] + s1;
-    }
-    const uint32_t S1 = rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25);
-    const uint32_t ch = (e & f) ^ (~e & g);
-    const uint32_t t1 = h + S1 + ch + K256.k[t] + w[t & 15];
-    const uint32_t S0 = rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22);
-    const uint32_t maj = (a & b) ^ (a & c) ^ (b & c);
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + S0 + maj;
-  }
-  s.h[0] += a, s.h[1] += b, s.h[2] += c, s.h[3] += d;
-  s.h[4] += e, s.h[5] += f, s.h[6] += g, s.h[7] += h;
-}
-
-// Compress the padded tail of a message whose first `prefix` bytes (a multiple of 64)
-// are already in s and whose remaining `len` bytes are byte_at(0 .. len-1).
-// word_over(b, t, w) may replace word t of tail block b (used for register-held data).
-template <class ByteAt, class WordOver>
-__device__ __forceinline__ void tail(H8& s, uint32_t prefix, uint32_t len, ByteAt byte_at, WordOver word_over) {
-  const uint32_t nblk = (len + 9 + 63) / 64;
-  const uint64_t bits = (uint64_t)(prefix + len) * 8;
-#pragma unroll 1
-  for (uint32_t b = 0; b < nblk; ++b) {
-    uint32_t w[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      uint32_t x = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t pos = 64 * b + 4 * t + k;
-        const uint32_t v = pos < len ? byte_at(pos) : (pos == len ? 0x80u : 0u);
-        x = (x << 8) | v;
-      }
-      w[t] = word_over(b, t, x);
-    }
-    if (b == nblk - 1) {
-      w[14] = (uint32_t)(bits >> 32);
-      w[15] = (uint32_t)bits;
-    }
-    compress(s, w);
-  }
-}
 
 __device__ __forceinline__ void pad_state(H8& s, const uint32_t k0[16], uint32_t pad) {
   uint32_t w[16];

@@ -229,6 +229,25 @@ hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* m
                         const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
                         const MldsaTrace& trace, void* scratch, hipStream_t st);
 
+// SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" verification over n rows of one chunk (slhdsa.hip).  which =
+// slhdsa_find(name): 2 set + flavour (set 0, 1, 2 = 128f, 192f, 256f; flavour 0 = "SPHINCS+-SHA2-*f-simple",
+// round 3.1; 1 = "SLH-DSA-SHA2-*f", FIPS 205), -1 for any other name.  Arguments as mldsa_verify; a context
+// string exists only in the FIPS 205 flavour.  The trace pointers are all set or all NULL (tests):
+// digest [n][m], fors_pk [n][n], roots [n][d][n], flags [n].
+struct SlhdsaTrace {
+  uint8_t* digest = nullptr;
+  uint8_t* fors_pk = nullptr;
+  uint8_t* roots = nullptr;
+  uint32_t* flags = nullptr;
+};
+int slhdsa_find(const char* name);
+bool slhdsa_is_fips(int which);
+void slhdsa_sizes(int which, size_t out[6]);  // pk, sk, sig, m (digest bytes), n, d
+size_t slhdsa_scratch_bytes(int which, size_t chunk);
+hipError_t slhdsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* msg, const uint64_t* msg_off,
+                         const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
+                         const SlhdsaTrace& trace, void* scratch, hipStream_t st);
+
 // Standard base64 (RFC 4648, '=' padding) of n records of L bytes -> [n][4 ceil(L/3)] chars,
 // and strict decoding back (status[i] = -1 for a malformed record; caller zeroes status).
 hipError_t base64_encode(size_t n, const uint8_t* in, size_t L, uint8_t* out, hipStream_t st);

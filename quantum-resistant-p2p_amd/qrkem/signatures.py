@@ -1,11 +1,13 @@
-"""ML-DSA signature verification on the GPU -- the verifying half of the reference's ``crypto/signatures.py``.
+"""Signature verification on the GPU -- the verifying half of the reference's ``crypto/signatures.py``.
 
 ``SignatureAlgorithm`` keeps the three abstract methods of ``quantum_resistant_p2p/crypto/signatures.py:
-18-55`` and ``MLDSASignature`` the names, strings and errors of ``:58-188``.  Only ``verify`` is
-implemented (``qrk_sig_verify_batch``, mldsa.hip: FIPS 204 pure ML-DSA with the empty context string,
-what liboqs's ``OQS_SIG_sign`` produces); ``generate_keypair`` and ``sign`` raise ``NotImplementedError``:
-a node keeps signing with liboqs and verifies the messages it receives here, in batches
-(:meth:`MLDSASignature.verify_batch`).  Like ``_native.py`` there is no CPU fallback.
+18-55``, ``MLDSASignature`` the names, strings and errors of ``:58-188`` and ``SPHINCSSignature`` those of
+``:191-314``.  Only ``verify`` is implemented (``qrk_sig_verify_batch``; mldsa.hip: FIPS 204 pure ML-DSA
+with the empty context string, what liboqs's ``OQS_SIG_sign`` produces; slhdsa.hip: the round-3.1
+``SPHINCS+-SHA2-*f-simple`` sets liboqs ships, or FIPS 205 pure SLH-DSA with ``fips205=True``);
+``generate_keypair`` and ``sign`` raise ``NotImplementedError``: a node keeps signing with liboqs and
+verifies the messages it receives here, in batches (:meth:`verify_batch`).  Like ``_native.py`` there is
+no CPU fallback.
 """
 from __future__ import annotations
 
@@ -30,6 +32,8 @@ logger = logging.getLogger(__name__)
 
 VERIFY_ONLY = ("qrkem verifies ML-DSA signatures only: {} stays with liboqs "
                "(libqrkem has no ML-DSA KeyGen or Sign)")
+SPHINCS_VERIFY_ONLY = ("qrkem verifies SPHINCS+ signatures only: {} stays with liboqs "
+                       "(libqrkem has no SPHINCS+ / SLH-DSA KeyGen or Sign)")
 
 
 class SignatureAlgorithm(CryptoAlgorithm):
@@ -49,40 +53,25 @@ class SignatureAlgorithm(CryptoAlgorithm):
 
 
 def sig_sizes(variant: str) -> Tuple[int, int, int]:
-    """(public key, secret key, signature) bytes of an ML-DSA parameter set."""
+    """(public key, secret key, signature) bytes of an ML-DSA or SLH-DSA / SPHINCS+ parameter set."""
     out = (ct.c_size_t * 3)()
     if LIB.qrk_sig_sizes(variant.encode(), out) != 0:
         raise ValueError(last_error())
     return int(out[0]), int(out[1]), int(out[2])
 
 
-class MLDSASignature(SignatureAlgorithm):
-    """ML-DSA (FIPS 204) verification on one device.  The context is created on first use, so
-    constructing the object (as the reference does at start-up, messaging.py:128) needs no GPU."""
+class _BatchVerifier(SignatureAlgorithm):
+    """What the verifying classes share: sizes from the library, the lazily created context, scalar
+    ``verify`` and the batch calls.  A subclass sets ``FAMILY`` (the name used in messages), ``VERIFY_ONLY``
+    and ``variant`` before calling :meth:`_setup`."""
 
-    VARIANTS = {2: "ML-DSA-44", 3: "ML-DSA-65", 5: "ML-DSA-87"}
+    FAMILY = ""
+    VERIFY_ONLY = ""
 
-    def __init__(self, security_level: int = 3, device: int = 0):
-        if security_level not in self.VARIANTS:
-            raise ValueError(f"Invalid security level: {security_level}. Must be 2, 3, or 5.")
-        self.security_level = security_level
-        self.variant = self.VARIANTS[security_level]
+    def _setup(self, device: int) -> None:
         self.device = device
         self.public_key_size, self.secret_key_size, self.signature_size = sig_sizes(self.variant)
         self._ctx = None
-
-    @property
-    def name(self) -> str:
-        return f"ML-DSA (Level {self.security_level})"
-
-    @property
-    def display_name(self) -> str:
-        return f"ML-DSA (Level {self.security_level})"
-
-    @property
-    def description(self) -> str:
-        return ("ML-DSA is a lattice-based digital signature scheme. "
-                "It is one of the NIST post-quantum cryptography standards.")
 
     def _context(self):
         if self._ctx is None:
@@ -105,10 +94,10 @@ class MLDSASignature(SignatureAlgorithm):
 
     # ------------------------------------------------------------------ the reference's single calls
     def generate_keypair(self) -> Tuple[bytes, bytes]:
-        raise NotImplementedError(VERIFY_ONLY.format("key generation"))
+        raise NotImplementedError(self.VERIFY_ONLY.format("key generation"))
 
     def sign(self, private_key: bytes, message: bytes) -> bytes:
-        raise NotImplementedError(VERIFY_ONLY.format("signing"))
+        raise NotImplementedError(self.VERIFY_ONLY.format("signing"))
 
     def verify(self, public_key: bytes, message: bytes, signature: bytes) -> bool:
         """True if the signature is valid.  Never raises: a wrong-length key or signature is False
@@ -118,7 +107,7 @@ class MLDSASignature(SignatureAlgorithm):
                 return False
             return bool(self.verify_batch([bytes(public_key)], [bytes(message)], [bytes(signature)])[0])
         except Exception as exc:
-            logger.error(f"Error verifying ML-DSA signature: {exc}")
+            logger.error(f"Error verifying {self.FAMILY} signature: {exc}")
             return False
 
     # ------------------------------------------------------------------ batches
@@ -149,12 +138,74 @@ class MLDSASignature(SignatureAlgorithm):
             public_keys = _dev(_as_host(public_keys, self.public_key_size), self.device)
         if not _is_dev(signatures):
             signatures = _dev(_as_host(signatures, self.signature_size), self.device)
-        _check_dev(public_keys, self.public_key_size, "ML-DSA public keys", n)
-        _check_dev(signatures, self.signature_size, "ML-DSA signatures", n)
+        _check_dev(public_keys, self.public_key_size, f"{self.FAMILY} public keys", n)
+        _check_dev(signatures, self.signature_size, f"{self.FAMILY} signatures", n)
         status = torch.empty((n,), dtype=torch.int32, device=messages.device)
         rc = LIB.qrk_sig_verify_batch(ctx, self.variant.encode(), n, _ptr(public_keys), _ptr(messages), _ptr(offsets),
                                       _ptr(signatures), None, 0, _ptr(status),
                                       ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         if rc != 0:
-            raise RuntimeError(f"qrkem ML-DSA verify failed ({self.variant}): {last_error()}")
+            raise RuntimeError(f"qrkem {self.FAMILY} verify failed ({self.variant}): {last_error()}")
         return status
+
+
+class MLDSASignature(_BatchVerifier):
+    """ML-DSA (FIPS 204) verification on one device.  The context is created on first use, so
+    constructing the object (as the reference does at start-up, messaging.py:128) needs no GPU."""
+
+    VARIANTS = {2: "ML-DSA-44", 3: "ML-DSA-65", 5: "ML-DSA-87"}
+    FAMILY = "ML-DSA"
+    VERIFY_ONLY = VERIFY_ONLY
+
+    def __init__(self, security_level: int = 3, device: int = 0):
+        if security_level not in self.VARIANTS:
+            raise ValueError(f"Invalid security level: {security_level}. Must be 2, 3, or 5.")
+        self.security_level = security_level
+        self.variant = self.VARIANTS[security_level]
+        self._setup(device)
+
+    @property
+    def name(self) -> str:
+        return f"ML-DSA (Level {self.security_level})"
+
+    @property
+    def display_name(self) -> str:
+        return f"ML-DSA (Level {self.security_level})"
+
+    @property
+    def description(self) -> str:
+        return ("ML-DSA is a lattice-based digital signature scheme. "
+                "It is one of the NIST post-quantum cryptography standards.")
+
+
+class SPHINCSSignature(_BatchVerifier):
+    """SPHINCS+ / SLH-DSA verification on one device, the SHA2 "f" parameter sets.  By default the variant
+    is the round-3.1 ``SPHINCS+-SHA2-*f-simple`` name the reference asks liboqs for (signatures.py:208-212);
+    ``fips205=True`` selects FIPS 205 pure SLH-DSA with the empty context string instead.  As for ML-DSA the
+    context is created on first use."""
+
+    VARIANTS = {1: "SPHINCS+-SHA2-128f-simple", 3: "SPHINCS+-SHA2-192f-simple", 5: "SPHINCS+-SHA2-256f-simple"}
+    FIPS_VARIANTS = {1: "SLH-DSA-SHA2-128f", 3: "SLH-DSA-SHA2-192f", 5: "SLH-DSA-SHA2-256f"}
+    FAMILY = "SPHINCS+"
+    VERIFY_ONLY = SPHINCS_VERIFY_ONLY
+
+    def __init__(self, security_level: int = 3, device: int = 0, fips205: bool = False):
+        if security_level not in self.VARIANTS:
+            raise ValueError(f"Invalid security level: {security_level}. Must be 1, 3, or 5.")
+        self.security_level = security_level
+        self.fips205 = bool(fips205)
+        self.variant = (self.FIPS_VARIANTS if self.fips205 else self.VARIANTS)[security_level]
+        self._setup(device)
+
+    @property
+    def name(self) -> str:
+        return f"SPHINCS+ (Level {self.security_level})"
+
+    @property
+    def display_name(self) -> str:
+        return f"SPHINCS+ (Level {self.security_level})"
+
+    @property
+    def description(self) -> str:
+        return ("SPHINCS+ is a stateless hash-based digital signature scheme. "
+                "Its security relies only on the security of the underlying hash functions.")
