@@ -294,6 +294,31 @@ int qrk_sig_verify_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t 
                          const uint64_t *msg_off, const uint8_t *sig, const uint8_t *ctx_str, size_t ctx_len,
                          int32_t *status, void *stream);
 
+/* SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" key generation and signing: the other half of the reference's
+ * SPHINCSSignature (signatures.py:238-292; sign is called on every key-exchange message and chat message,
+ * messaging.py:620, 864, 1090).  alg: the six hash-based names of qrk_sig_sizes.  An ML-DSA name returns -1
+ * with a message naming it (qrkem has no ML-DSA KeyGen or Sign), any other name -1 "unsupported signature
+ * algorithm".  Checked before any device work, in this order: null context, name, ctx_len > 255, a context
+ * under a "SPHINCS+-" name; then n == 0 returns 0.  Device pointers, stream-ordered on `stream`.  Output is
+ * byte-exact FIPS 205 Algorithm 18 / 19 (and the round-3.1 submission's) for the given seeds and opt_rand.
+ * Rows per launch follow qrk_ctx_set_chunk (at most 65536); the context's scratch grows on demand by 950 /
+ * 1462 / 1813 bytes per row (128f / 192f / 256f) and holds public values only: the H_msg digest, a flag
+ * word, the hash states after PK.seed, the k FORS roots and the d XMSS roots.  SK.seed and SK.prf are read
+ * from `sk` (KeyGen: from the sk being written) and never copied anywhere else.
+ *
+ * KeyGen: seeds [n][3 n_bytes] = SK.seed || SK.prf || PK.seed per row (n_bytes = 16 / 24 / 32; FIPS 205
+ * Algorithm 18, the caller draws them); pk [n][pk bytes] = PK.seed || PK.root, sk [n][sk bytes] = seeds || PK.root. */
+int qrk_sig_keypair_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *seeds, uint8_t *pk, uint8_t *sk,
+                          void *stream);
+/* Sign: sk [n][sk bytes]; messages ragged and ctx_str / ctx_len as qrk_sig_verify_batch; opt_rand NULL =
+ * the deterministic variant (opt_rand = PK.seed), else [n][n_bytes] fresh random bytes per row (hedged);
+ * sig [n][sig bytes].  status (required, int32[n]): 0, or -1 with an all-zero signature row for a row of 2^31
+ * bytes or more, a row whose offsets decrease, or a secret key whose PK.root is not the root its SK.seed
+ * and PK.seed give (a corrupt key); every row is written exactly once. */
+int qrk_sig_sign_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *msg,
+                       const uint64_t *msg_off, const uint8_t *opt_rand, const uint8_t *ctx_str, size_t ctx_len,
+                       uint8_t *sig, int32_t *status, void *stream);
+
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853
  * ciphertext and responder key; decoded at :829 with base64.b64decode).  Device pointers,

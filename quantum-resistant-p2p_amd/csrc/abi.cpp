@@ -1393,6 +1393,71 @@ int qrk_sig_verify_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t*
   return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, SigTrace{}, stream);
 }
 
+// ------------------------------------------------------------------ key generation and signing (slhdsa_sign.hip)
+// The argument checks the two calls share, in the documented order; `a` is set on success.
+static int sig_sign_find(qrk_ctx* ctx, const char* alg, size_t ctx_len, SigAlg& a) {
+  if (!ctx) return fail("null context");
+  a = sig_find(alg);
+  if (a.family == SigFamily::NONE) return sig_unsupported(alg);
+  if (a.family == SigFamily::MLDSA)
+    return fail(std::string(alg) + ": qrkem has no ML-DSA KeyGen or Sign (verification only; signing stays with liboqs)");
+  if (ctx_len > 255) return fail("SLH-DSA context strings are at most 255 bytes");
+  if (ctx_len && !slhdsa_is_fips(a.which))
+    return fail(std::string(alg) + " is the round-3.1 submission, which has no context string (ctx_len must be 0; "
+                                   "the SLH-DSA-SHA2-* names take one)");
+  return 0;
+}
+// rows per launch: the context's chunk, at most what one grid takes; equal multiples of 64 and a shorter tail
+static size_t sig_sign_chunk(const qrk_ctx* ctx, size_t n) {
+  return chunk_plan(n, std::min(ctx->chunk, SLHDSA_SIGN_MAX_ROWS));
+}
+
+int qrk_sig_keypair_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* seeds, uint8_t* pk, uint8_t* sk,
+                          void* stream) {
+  SigAlg a;
+  if (sig_sign_find(ctx, alg, 0, a)) return -1;
+  if (n == 0) return 0;
+  if (!seeds || !pk || !sk) return fail("null buffer");
+  hipStream_t st = (hipStream_t)stream;
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
+  size_t sz[6];
+  slhdsa_sizes(a.which, sz);
+  const size_t chunk = sig_sign_chunk(ctx, n);
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, slhdsa_sign_scratch_bytes(a.which, chunk), st)) return -1;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = std::min(chunk, n - off);
+    launch_begin();
+    hipError_t e = slhdsa_keypair(a.which, m, seeds + off * 3 * sz[4], pk + off * sz[0], sk + off * sz[1], ctx->scratch, st);
+    if (e != hipSuccess) return hip_fail("slhdsa_keypair", e);
+  }
+  return 0;
+}
+
+int qrk_sig_sign_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                       const uint64_t* msg_off, const uint8_t* opt_rand, const uint8_t* ctx_str, size_t ctx_len,
+                       uint8_t* sig, int32_t* status, void* stream) {
+  SigAlg a;
+  if (sig_sign_find(ctx, alg, ctx_len, a)) return -1;
+  if (n == 0) return 0;
+  if (!sk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
+  hipStream_t st = (hipStream_t)stream;
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
+  size_t sz[6];
+  slhdsa_sizes(a.which, sz);
+  const size_t chunk = sig_sign_chunk(ctx, n);
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, slhdsa_sign_scratch_bytes(a.which, chunk), st)) return -1;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = std::min(chunk, n - off);
+    launch_begin();
+    hipError_t e = slhdsa_sign(a.which, m, sk + off * sz[1], msg, msg_off + off, opt_rand ? opt_rand + off * sz[4] : nullptr,
+                               ctx_str, ctx_len, sig + off * sz[2], status + off, ctx->scratch, st);
+    if (e != hipSuccess) return hip_fail("slhdsa_sign", e);
+  }
+  return 0;
+}
+
 // Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed
 // c~' [n][64] (lambda / 4 bytes, then zeros), the w1Encode bytes [n][k 32 (6 or 4)] and a flag word
 // (bit 0: hint encoding malformed, bit 1: ||z||_inf >= gamma1 - beta, bit 2: c~ != c~'; bit 3, internal:

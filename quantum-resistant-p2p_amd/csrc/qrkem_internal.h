@@ -248,6 +248,19 @@ hipError_t slhdsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* 
                          const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
                          const SlhdsaTrace& trace, void* scratch, hipStream_t st);
 
+// SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" key generation and signing over n <= SLHDSA_SIGN_MAX_ROWS rows of one
+// chunk (slhdsa_sign.hip); which as above.  seeds [n][3 n_bytes] = SK.seed || SK.prf || PK.seed; opt_rand NULL
+// (deterministic: PK.seed) or [n][n_bytes]; status[i] = 0, or -1 with an all-zero signature row (a row of
+// 2^31 bytes or more, decreasing offsets, or a key whose PK.root is not the root of its SK.seed).  The scratch
+// holds public values only (slhdsa_sign_scratch_bytes: 0.9 to 1.8 KB per row).
+constexpr size_t SLHDSA_SIGN_MAX_ROWS = (size_t)1 << 16;  // rows are grid.x of (rows, trees) launches
+size_t slhdsa_sign_scratch_bytes(int which, size_t chunk);
+hipError_t slhdsa_keypair(int which, size_t n, const uint8_t* seeds, uint8_t* pk, uint8_t* sk, void* scratch,
+                          hipStream_t st);
+hipError_t slhdsa_sign(int which, size_t n, const uint8_t* sk, const uint8_t* msg, const uint64_t* msg_off,
+                       const uint8_t* opt_rand, const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig, int32_t* status,
+                       void* scratch, hipStream_t st);
+
 // Standard base64 (RFC 4648, '=' padding) of n records of L bytes -> [n][4 ceil(L/3)] chars,
 // and strict decoding back (status[i] = -1 for a malformed record; caller zeroes status).
 hipError_t base64_encode(size_t n, const uint8_t* in, size_t L, uint8_t* out, hipStream_t st);

@@ -1,4 +1,5 @@
-"""Signature verification on the GPU -- the verifying half of the reference's ``crypto/signatures.py``.
+"""Signatures on the GPU -- the reference's ``crypto/signatures.py``: verification for ML-DSA and SPHINCS+ /
+SLH-DSA, and for the hash-based family key generation and signing as well.
 
 ``SignatureAlgorithm`` keeps the three abstract methods of ``quantum_resistant_p2p/crypto/signatures.py:
 18-55``, ``MLDSASignature`` the names, strings and errors of ``:58-188`` and ``SPHINCSSignature`` those of
@@ -6,14 +7,21 @@
 with the empty context string, what liboqs's ``OQS_SIG_sign`` produces; slhdsa.hip: the round-3.1
 ``SPHINCS+-SHA2-*f-simple`` sets liboqs ships, or FIPS 205 pure SLH-DSA with ``fips205=True``);
 ``generate_keypair`` and ``sign`` raise ``NotImplementedError``: a node keeps signing with liboqs and
-verifies the messages it receives here, in batches (:meth:`verify_batch`).  Like ``_native.py`` there is
-no CPU fallback.
+verifies the messages it receives here, in batches (:meth:`verify_batch`).  That is every default constructor.
+
+``SPHINCSSignature(signing=True)`` implements the other half too (``qrk_sig_keypair_batch`` /
+``qrk_sig_sign_batch``, slhdsa_sign.hip: FIPS 205 Algorithms 18 and 19): ``generate_keypair`` and ``sign`` as
+the reference calls them, :meth:`SPHINCSSignature.generate_keypair_batch` and
+:meth:`SPHINCSSignature.sign_batch` over device tensors.  Signing is hedged (a fresh ``opt_rand`` per
+signature) unless ``deterministic=True``.  A node on the SPHINCS+ path then needs no liboqs; ML-DSA signing
+still does.  Like ``_native.py`` there is no CPU fallback.
 """
 from __future__ import annotations
 
 import abc
 import ctypes as ct
 import logging
+import os
 from typing import Tuple
 
 import numpy as np
@@ -179,23 +187,115 @@ class MLDSASignature(_BatchVerifier):
 
 
 class SPHINCSSignature(_BatchVerifier):
-    """SPHINCS+ / SLH-DSA verification on one device, the SHA2 "f" parameter sets.  By default the variant
-    is the round-3.1 ``SPHINCS+-SHA2-*f-simple`` name the reference asks liboqs for (signatures.py:208-212);
-    ``fips205=True`` selects FIPS 205 pure SLH-DSA with the empty context string instead.  As for ML-DSA the
-    context is created on first use."""
+    """SPHINCS+ / SLH-DSA on one device, the SHA2 "f" parameter sets.  By default the variant is the round-3.1
+    ``SPHINCS+-SHA2-*f-simple`` name the reference asks liboqs for (signatures.py:208-212); ``fips205=True``
+    selects FIPS 205 pure SLH-DSA with the empty context string instead.  As for ML-DSA the context is created
+    on first use.  Verification only by default; ``signing=True`` adds key generation and signing on the GPU
+    (hedged; ``deterministic=True`` signs with opt_rand = PK.seed, which reproduces a signature bit for bit)."""
 
     VARIANTS = {1: "SPHINCS+-SHA2-128f-simple", 3: "SPHINCS+-SHA2-192f-simple", 5: "SPHINCS+-SHA2-256f-simple"}
     FIPS_VARIANTS = {1: "SLH-DSA-SHA2-128f", 3: "SLH-DSA-SHA2-192f", 5: "SLH-DSA-SHA2-256f"}
     FAMILY = "SPHINCS+"
     VERIFY_ONLY = SPHINCS_VERIFY_ONLY
 
-    def __init__(self, security_level: int = 3, device: int = 0, fips205: bool = False):
+    def __init__(self, security_level: int = 3, device: int = 0, fips205: bool = False, signing: bool = False,
+                 deterministic: bool = False):
         if security_level not in self.VARIANTS:
             raise ValueError(f"Invalid security level: {security_level}. Must be 1, 3, or 5.")
         self.security_level = security_level
         self.fips205 = bool(fips205)
+        self.signing = bool(signing)
+        self.deterministic = bool(deterministic)
         self.variant = (self.FIPS_VARIANTS if self.fips205 else self.VARIANTS)[security_level]
         self._setup(device)
+        self.n_bytes = self.public_key_size // 2
+
+    # ------------------------------------------------------------------ key generation and signing (signing=True)
+    def _stream(self):
+        return ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def generate_keypair(self) -> Tuple[bytes, bytes]:
+        """(public key, secret key) from 3 n fresh bytes of the OS CSPRNG (signatures.py:238-259)."""
+        if not self.signing:
+            return super().generate_keypair()
+        pk, sk = self.generate_keypair_batch(1)
+        return pk[0].cpu().numpy().tobytes(), sk[0].cpu().numpy().tobytes()
+
+    def sign(self, private_key: bytes, message: bytes) -> bytes:
+        """The signature of `message`.  Unlike ``verify`` this raises on any error, as the reference's does
+        (signatures.py:290-292)."""
+        if not self.signing:
+            return super().sign(private_key, message)
+        ctx = self._context()  # noqa: F841  (first: without a device this is the error to raise)
+        if len(private_key) != self.secret_key_size:
+            raise ValueError(f"{self.FAMILY} secret keys of {self.variant} have {self.secret_key_size} bytes, "
+                             f"got {len(private_key)}")
+        return self.sign_batch([bytes(private_key)], [bytes(message)])[0].cpu().numpy().tobytes()
+
+    def generate_keypair_batch(self, n: int, seeds=None):
+        """n key pairs: device tensors (pk [n, pk bytes], sk [n, sk bytes]).  ``seeds``: [n, 3 n_bytes] uint8 =
+        SK.seed || SK.prf || PK.seed per row (a device tensor, numpy array or list of bytes); None draws them
+        from ``os.urandom``."""
+        if not self.signing:
+            return super().generate_keypair()
+        ctx = self._context()
+        width = 3 * self.n_bytes
+        if seeds is None:
+            seeds = np.frombuffer(os.urandom(n * width), np.uint8).reshape(n, width)
+        if not _is_dev(seeds):
+            seeds = _dev(_as_host(seeds, width), self.device)
+        _check_dev(seeds, width, f"{self.FAMILY} key seeds", n)
+        pk = torch.empty((n, self.public_key_size), dtype=torch.uint8, device=seeds.device)
+        sk = torch.empty((n, self.secret_key_size), dtype=torch.uint8, device=seeds.device)
+        rc = LIB.qrk_sig_keypair_batch(ctx, self.variant.encode(), n, _ptr(seeds), _ptr(pk), _ptr(sk), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} key generation failed ({self.variant}): {last_error()}")
+        return pk, sk
+
+    def sign_batch(self, private_keys, messages, offsets=None, opt_rand=None, return_status: bool = False):
+        """sig[i] = Sign(private_keys[i], messages[i]): a uint8 device tensor [n, signature bytes].
+
+        ``private_keys`` [n, sk bytes] and ``messages`` / ``offsets`` as in :meth:`verify_status`.  ``opt_rand``
+        [n, n_bytes]: the per-row randomiser; None draws it from ``os.urandom``, or uses PK.seed (the
+        deterministic variant of FIPS 205) if the object was made with ``deterministic=True``.  A row the
+        library refuses (status -1: offsets that decrease, 2^31 bytes or more, a corrupt key) has an all-zero
+        signature; that raises ``RuntimeError`` unless ``return_status=True``, which returns
+        ``(signatures, status)`` with the int32 [n] device tensor instead."""
+        if not self.signing:
+            return super().sign(b"", b"")
+        ctx = self._context()
+        if offsets is None:
+            data, off = pack_infos([bytes(m) for m in messages])
+            messages, offsets = _dev(data, self.device), _dev(off.view(np.int64), self.device)
+        n = offsets.numel() - 1
+        if not (_is_dev(messages) and messages.dtype == torch.uint8 and messages.dim() == 1 and
+                messages.is_contiguous()):
+            raise ValueError("messages must be a contiguous 1-D uint8 device tensor")
+        if not (_is_dev(offsets) and offsets.dtype in (torch.int64, torch.uint64) and offsets.dim() == 1 and
+                n >= 0 and offsets.is_contiguous()):
+            raise ValueError("offsets must be a contiguous 64-bit device tensor of n + 1 entries")
+        if not _is_dev(private_keys):
+            private_keys = _dev(_as_host(private_keys, self.secret_key_size), self.device)
+        _check_dev(private_keys, self.secret_key_size, f"{self.FAMILY} secret keys", n)
+        if opt_rand is None and not self.deterministic:
+            opt_rand = np.frombuffer(os.urandom(n * self.n_bytes), np.uint8).reshape(n, self.n_bytes)
+        if opt_rand is not None:
+            if not _is_dev(opt_rand):
+                opt_rand = _dev(_as_host(opt_rand, self.n_bytes), self.device)
+            _check_dev(opt_rand, self.n_bytes, f"{self.FAMILY} opt_rand", n)
+        sig = torch.empty((n, self.signature_size), dtype=torch.uint8, device=messages.device)
+        status = torch.empty((n,), dtype=torch.int32, device=messages.device)
+        rc = LIB.qrk_sig_sign_batch(ctx, self.variant.encode(), n, _ptr(private_keys), _ptr(messages), _ptr(offsets),
+                                    _ptr(opt_rand), None, 0, _ptr(sig), _ptr(status), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {last_error()}")
+        if return_status:
+            return sig, status
+        bad = int((status != 0).sum())  # the one host wait of this path
+        if bad:
+            raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {bad} of {n} rows were refused "
+                               "(corrupt secret key or malformed message offsets)")
+        return sig
 
     @property
     def name(self) -> str:
