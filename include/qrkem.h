@@ -82,10 +82,12 @@ OQS_STATUS OQS_KEM_encaps_derand(const OQS_KEM *kem, uint8_t *ciphertext, uint8_
                                  const uint8_t *public_key, const uint8_t *seed);
 
 /* Signature half of the liboqs ABI: the reference's oqs.py binds these at
- * import time (oqs.py:684-697).  The engine has no KeyGen or Sign, and an
- * OQS_SIG that could only verify would be a trap, so the registry stays empty
- * (count 0) and every call here fails.  Batched ML-DSA verification is
- * qrk_sig_verify_batch in Part 2. */
+ * import time (oqs.py:684-697).  The engine has no ML-DSA KeyGen or Sign, and
+ * an OQS_SIG that could only verify would be a trap; the hash-based family,
+ * which it can sign with, has no single-shot path here.  So the registry stays
+ * empty (count 0) and every call here fails.  The batched calls of Part 2
+ * verify for both families (qrk_sig_verify_batch) and generate keys and sign
+ * for the hash-based one (qrk_sig_keypair_batch, qrk_sig_sign_batch). */
 typedef struct OQS_SIG OQS_SIG;
 size_t OQS_SIG_alg_count(void);
 const char *OQS_SIG_alg_identifier(size_t i);
@@ -270,8 +272,9 @@ int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
 /* ML-DSA signature verification (FIPS 204 final, "pure" ML-DSA: Verify, Algorithm 3), the step the
  * reference runs on every handshake and chat message (signatures.py:167 from messaging.py:721, 933,
  * 1174, 1480).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; any other name returns -1 with
- * qrk_last_error() set.  Verification only: there is no KeyGen or Sign (the OQS_SIG registry of
- * Part 1 stays empty).
+ * qrk_last_error() set.  For ML-DSA verification only: there is no ML-DSA KeyGen or Sign (and the
+ * OQS_SIG registry of Part 1 stays empty); the hash-based names below also have
+ * qrk_sig_keypair_batch and qrk_sig_sign_batch.
  * The same two calls verify hash-based signatures, the SHA2 "f" parameter sets, in two flavours:
  * "SPHINCS+-SHA2-128f-simple", "SPHINCS+-SHA2-192f-simple", "SPHINCS+-SHA2-256f-simple" (the round-3.1
  * submission as liboqs ships it, what the reference's SPHINCSSignature asks for, signatures.py:208-212)

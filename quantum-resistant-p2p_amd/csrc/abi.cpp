@@ -308,13 +308,12 @@ struct CallOpts {
 #ifndef QRK_SCRATCH_GIB
 #define QRK_SCRATCH_GIB 48
 #endif
+static size_t scratch_cap(size_t per_row) {
+  return std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_row / 64 * 64);
+}
 static size_t chunk_for(const qrk_ctx* ctx, const AlgInfo& a) {
-  size_t cap = ctx->chunk;
-  if (a.family != Family::MLKEM) {
-    const size_t per_hs = ops_of(a).scratch_bytes(a, 1024) / 1024 + 1;
-    cap = std::min(cap, std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_hs / 64 * 64));
-  }
-  return cap;
+  if (a.family == Family::MLKEM) return ctx->chunk;
+  return std::min(ctx->chunk, scratch_cap(ops_of(a).scratch_bytes(a, 1024) / 1024 + 1));
 }
 
 // Equal chunks (multiples of 64) of at most `cap` handshakes rather than full chunks plus a small tail.
@@ -495,6 +494,24 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     // key material of this chunk (seeds, m', K', Kbar, ...) does not outlive the call
     e = f.cleanse(a, m, ctx->scratch, st);
     if (e != hipSuccess) return hip_fail("hipMemsetAsync(cleanse)", e);
+  }
+  return 0;
+}
+
+// The row driver of the signature calls (outermost: it takes the lock): n > 0 rows through a launcher that uses the
+// context's scratch (public values only: no cleanse), in equal chunks of at most min(qrk_ctx_set_chunk, cap) rows.
+// launch(off, m) runs rows [off, off + m); the first failing chunk's status is the call's error, named `what`.
+template <class Launch>
+static int run_rows(qrk_ctx* ctx, hipStream_t st, size_t n, size_t cap, size_t (*scratch_bytes)(int, size_t), int which,
+                    const char* what, Launch launch) {
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
+  const size_t chunk = chunk_plan(n, std::min(ctx->chunk, cap));
+  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_bytes(which, chunk), st)) return -1;
+  for (size_t off = 0; off < n; off += chunk) {
+    launch_begin();
+    const hipError_t e = launch(off, std::min(chunk, n - off));
+    if (e != hipSuccess) return hip_fail(what, e);
   }
   return 0;
 }
@@ -1295,19 +1312,20 @@ extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* da
   return e == hipSuccess ? 0 : hip_fail("dbg_ghash", e);
 }
 
-// ------------------------------------------------------------------ signature verification (mldsa.hip, slhdsa.hip)
-// One family lookup for both entry points: ML-DSA first, then SLH-DSA / SPHINCS+.
-enum class SigFamily { NONE, MLDSA, SLHDSA };
+// ------------------------------------------------------------------ signatures (mldsa.hip, slhdsa.hip, slhdsa_sign.hip)
+// One family lookup for every entry point: ML-DSA first, then SLH-DSA / SPHINCS+.
+enum { SIG_ANY = -1, SIG_MLDSA, SIG_SLHDSA };
 struct SigAlg {
-  SigFamily family = SigFamily::NONE;
+  int family = SIG_ANY;  // SIG_ANY: no family has the name
   int which = -1;
+  SigSizes sz{};
 };
 static SigAlg sig_find(const char* alg) {
   SigAlg a;
   if ((a.which = mldsa_find(alg)) >= 0)
-    a.family = SigFamily::MLDSA;
+    a.family = SIG_MLDSA, a.sz = mldsa_sizes(a.which);
   else if ((a.which = slhdsa_find(alg)) >= 0)
-    a.family = SigFamily::SLHDSA;
+    a.family = SIG_SLHDSA, a.sz = slhdsa_sizes(a.which);
   return a;
 }
 static int sig_unsupported(const char* alg) {
@@ -1316,146 +1334,96 @@ static int sig_unsupported(const char* alg) {
 
 int qrk_sig_sizes(const char* alg, size_t out[3]) {
   const SigAlg a = sig_find(alg);
-  if (a.family == SigFamily::NONE || !out) return sig_unsupported(alg);
-  size_t s[6];
-  if (a.family == SigFamily::MLDSA)
-    mldsa_sizes(a.which, s);
-  else
-    slhdsa_sizes(a.which, s);
-  out[0] = s[0], out[1] = s[1], out[2] = s[2];
+  if (a.family == SIG_ANY || !out) return sig_unsupported(alg);
+  out[0] = a.sz.pk, out[1] = a.sz.sk, out[2] = a.sz.sig;
   return 0;
 }
 
-// The traces of the two families' test hooks; `family` says which hook is calling (NONE: the public call).
-struct SigTrace {
-  SigFamily family = SigFamily::NONE;
-  MldsaTrace mldsa;
-  SlhdsaTrace slhdsa;
-};
-
-// ML-DSA's scratch is k l KiB + about 1.3 KB per row (A_hat, mu, w1, c, flags), SLH-DSA's the digest and a
-// flag word (38 to 53 bytes): chunks are capped like the families' (chunk_for) and run as equal multiples
-// of 64 with a shorter tail.
-static int sig_verify(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
-                      const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
-                      int32_t* status, const SigTrace& trace, void* stream) {
+// The argument checks of every signature call in the order qrkem.h documents (a trace hook takes its own `family`
+// only, a signing call no ML-DSA name; `bufs`: no required pointer is null).  -1: failed, 1: n == 0, 0: go, `a` set.
+static int sig_args(qrk_ctx* ctx, const char* alg, int family, bool signing, size_t ctx_len, size_t n, bool bufs,
+                    SigAlg& a) {
   if (!ctx) return fail("null context");
-  const SigAlg a = sig_find(alg);
-  if (a.family == SigFamily::NONE || (trace.family != SigFamily::NONE && trace.family != a.family))
-    return sig_unsupported(alg);
-  const bool dsa = a.family == SigFamily::MLDSA;
-  if (ctx_len > 255) return fail(dsa ? "ML-DSA context strings are at most 255 bytes"
-                                     : "SLH-DSA context strings are at most 255 bytes");
-  if (!dsa && ctx_len && !slhdsa_is_fips(a.which))
+  a = sig_find(alg);
+  if (a.family == SIG_ANY || (family != SIG_ANY && family != a.family)) return sig_unsupported(alg);
+  if (signing && a.family == SIG_MLDSA)
+    return fail(std::string(alg) + ": qrkem has no ML-DSA KeyGen or Sign (verification only; signing stays with liboqs)");
+  if (ctx_len > 255) return fail(a.family == SIG_MLDSA ? "ML-DSA context strings are at most 255 bytes"
+                                                       : "SLH-DSA context strings are at most 255 bytes");
+  if (a.family == SIG_SLHDSA && ctx_len && !slhdsa_is_fips(a.which))
     return fail(std::string(alg) + " is the round-3.1 submission, which has no context string (ctx_len must be 0; "
                                    "the SLH-DSA-SHA2-* names take one)");
-  if (n == 0) return 0;
-  if (!pk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
-  hipStream_t st = (hipStream_t)stream;
-  CallScope scope;
-  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
-  size_t sz[6];
-  if (dsa)
-    mldsa_sizes(a.which, sz);
-  else
-    slhdsa_sizes(a.which, sz);
-  auto scratch_bytes = [&](size_t rows) {
-    return dsa ? mldsa_scratch_bytes(a.which, rows) : slhdsa_scratch_bytes(a.which, rows);
-  };
-  const size_t per_row = scratch_bytes(1);
-  const size_t cap = std::min({ctx->chunk, (size_t)1 << 20,
-                               std::max<size_t>(4096, ((size_t)QRK_SCRATCH_GIB << 30) / per_row / 64 * 64)});
-  const size_t chunk = chunk_plan(n, cap);
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, scratch_bytes(chunk), st)) return -1;
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t m = std::min(chunk, n - off);
-    launch_begin();
-    if (dsa) {
-      MldsaTrace t = trace.mldsa;
-      if (t.flags) t.mu += off * 64, t.ctilde += off * 64, t.w1 += off * sz[3], t.flags += off;
-      hipError_t e = mldsa_verify(a.which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str,
-                                  ctx_len, status + off, t, ctx->scratch, st);
-      if (e != hipSuccess) return hip_fail("mldsa_verify", e);
-    } else {
-      SlhdsaTrace t = trace.slhdsa;
-      if (t.flags) t.digest += off * sz[3], t.fors_pk += off * sz[4], t.roots += off * sz[5] * sz[4], t.flags += off;
-      hipError_t e = slhdsa_verify(a.which, m, pk + off * sz[0], msg, msg_off + off, sig + off * sz[2], ctx_str,
-                                   ctx_len, status + off, t, ctx->scratch, st);
-      if (e != hipSuccess) return hip_fail("slhdsa_verify", e);
-    }
-  }
-  return 0;
+  if (n == 0) return 1;
+  return bufs ? 0 : fail("null buffer");
+}
+
+// Verification, one call site per family behind the public call and that family's trace hook.  Chunks are capped
+// like the KEM families' (ML-DSA's scratch: k l KiB + 1.3 KB per row; SLH-DSA's: 38 to 53 bytes) and at 2^20 rows.
+struct VerifyIo {  // the arguments of qrk_sig_verify_batch that a chunk's launcher sees
+  const uint8_t *pk, *msg;
+  const uint64_t* msg_off;
+  const uint8_t *sig, *ctx_str;
+  size_t ctx_len;
+  int32_t* status;
+  bool set() const { return pk && msg && msg_off && sig && status && (ctx_str || !ctx_len); }
+};
+static size_t verify_cap(size_t per_row) { return std::min((size_t)1 << 20, scratch_cap(per_row)); }
+
+static int mldsa_verify_rows(qrk_ctx* ctx, const SigAlg& a, size_t n, const VerifyIo& v, const MldsaTrace& trace,
+                             hipStream_t st) {
+  return run_rows(ctx, st, n, verify_cap(mldsa_scratch_bytes(a.which, 1)), mldsa_scratch_bytes, a.which, "mldsa_verify",
+                  [&](size_t off, size_t m) {
+                    return mldsa_verify(a.which, m, v.pk + off * a.sz.pk, v.msg, v.msg_off + off, v.sig + off * a.sz.sig,
+                                        v.ctx_str, v.ctx_len, v.status + off, mldsa_trace_at(a.which, trace, off),
+                                        ctx->scratch, st);
+                  });
+}
+static int slhdsa_verify_rows(qrk_ctx* ctx, const SigAlg& a, size_t n, const VerifyIo& v, const SlhdsaTrace& trace,
+                              hipStream_t st) {
+  return run_rows(ctx, st, n, verify_cap(slhdsa_scratch_bytes(a.which, 1)), slhdsa_scratch_bytes, a.which,
+                  "slhdsa_verify", [&](size_t off, size_t m) {
+                    return slhdsa_verify(a.which, m, v.pk + off * a.sz.pk, v.msg, v.msg_off + off, v.sig + off * a.sz.sig,
+                                         v.ctx_str, v.ctx_len, v.status + off, slhdsa_trace_at(a.which, trace, off),
+                                         ctx->scratch, st);
+                  });
 }
 
 int qrk_sig_verify_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
                          const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
                          int32_t* status, void* stream) {
-  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, SigTrace{}, stream);
+  const VerifyIo v{pk, msg, msg_off, sig, ctx_str, ctx_len, status};
+  SigAlg a;
+  if (const int r = sig_args(ctx, alg, SIG_ANY, false, ctx_len, n, v.set(), a)) return r < 0 ? -1 : 0;
+  return a.family == SIG_MLDSA ? mldsa_verify_rows(ctx, a, n, v, MldsaTrace{}, (hipStream_t)stream)
+                               : slhdsa_verify_rows(ctx, a, n, v, SlhdsaTrace{}, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------ key generation and signing (slhdsa_sign.hip)
-// The argument checks the two calls share, in the documented order; `a` is set on success.
-static int sig_sign_find(qrk_ctx* ctx, const char* alg, size_t ctx_len, SigAlg& a) {
-  if (!ctx) return fail("null context");
-  a = sig_find(alg);
-  if (a.family == SigFamily::NONE) return sig_unsupported(alg);
-  if (a.family == SigFamily::MLDSA)
-    return fail(std::string(alg) + ": qrkem has no ML-DSA KeyGen or Sign (verification only; signing stays with liboqs)");
-  if (ctx_len > 255) return fail("SLH-DSA context strings are at most 255 bytes");
-  if (ctx_len && !slhdsa_is_fips(a.which))
-    return fail(std::string(alg) + " is the round-3.1 submission, which has no context string (ctx_len must be 0; "
-                                   "the SLH-DSA-SHA2-* names take one)");
-  return 0;
-}
-// rows per launch: the context's chunk, at most what one grid takes; equal multiples of 64 and a shorter tail
-static size_t sig_sign_chunk(const qrk_ctx* ctx, size_t n) {
-  return chunk_plan(n, std::min(ctx->chunk, SLHDSA_SIGN_MAX_ROWS));
-}
-
+// Key generation and signing (slhdsa_sign.hip): at most SLHDSA_SIGN_MAX_ROWS rows per launch, what one grid takes.
 int qrk_sig_keypair_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* seeds, uint8_t* pk, uint8_t* sk,
                           void* stream) {
   SigAlg a;
-  if (sig_sign_find(ctx, alg, 0, a)) return -1;
-  if (n == 0) return 0;
-  if (!seeds || !pk || !sk) return fail("null buffer");
+  if (const int r = sig_args(ctx, alg, SIG_ANY, true, 0, n, seeds && pk && sk, a)) return r < 0 ? -1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  CallScope scope;
-  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
-  size_t sz[6];
-  slhdsa_sizes(a.which, sz);
-  const size_t chunk = sig_sign_chunk(ctx, n);
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, slhdsa_sign_scratch_bytes(a.which, chunk), st)) return -1;
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t m = std::min(chunk, n - off);
-    launch_begin();
-    hipError_t e = slhdsa_keypair(a.which, m, seeds + off * 3 * sz[4], pk + off * sz[0], sk + off * sz[1], ctx->scratch, st);
-    if (e != hipSuccess) return hip_fail("slhdsa_keypair", e);
-  }
-  return 0;
+  return run_rows(ctx, st, n, SLHDSA_SIGN_MAX_ROWS, slhdsa_sign_scratch_bytes, a.which, "slhdsa_keypair",
+                  [&](size_t off, size_t m) {
+                    return slhdsa_keypair(a.which, m, seeds + off * 3 * a.sz.n, pk + off * a.sz.pk, sk + off * a.sz.sk,
+                                          ctx->scratch, st);
+                  });
 }
 
 int qrk_sig_sign_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
                        const uint64_t* msg_off, const uint8_t* opt_rand, const uint8_t* ctx_str, size_t ctx_len,
                        uint8_t* sig, int32_t* status, void* stream) {
   SigAlg a;
-  if (sig_sign_find(ctx, alg, ctx_len, a)) return -1;
-  if (n == 0) return 0;
-  if (!sk || !msg || !msg_off || !sig || !status || (!ctx_str && ctx_len)) return fail("null buffer");
+  const bool bufs = sk && msg && msg_off && sig && status && (ctx_str || !ctx_len);
+  if (const int r = sig_args(ctx, alg, SIG_ANY, true, ctx_len, n, bufs, a)) return r < 0 ? -1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  CallScope scope;
-  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return -1;
-  size_t sz[6];
-  slhdsa_sizes(a.which, sz);
-  const size_t chunk = sig_sign_chunk(ctx, n);
-  if (grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, slhdsa_sign_scratch_bytes(a.which, chunk), st)) return -1;
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t m = std::min(chunk, n - off);
-    launch_begin();
-    hipError_t e = slhdsa_sign(a.which, m, sk + off * sz[1], msg, msg_off + off, opt_rand ? opt_rand + off * sz[4] : nullptr,
-                               ctx_str, ctx_len, sig + off * sz[2], status + off, ctx->scratch, st);
-    if (e != hipSuccess) return hip_fail("slhdsa_sign", e);
-  }
-  return 0;
+  return run_rows(ctx, st, n, SLHDSA_SIGN_MAX_ROWS, slhdsa_sign_scratch_bytes, a.which, "slhdsa_sign",
+                  [&](size_t off, size_t m) {
+                    return slhdsa_sign(a.which, m, sk + off * a.sz.sk, msg, msg_off + off,
+                                       opt_rand ? opt_rand + off * a.sz.n : nullptr, ctx_str, ctx_len, sig + off * a.sz.sig,
+                                       status + off, ctx->scratch, st);
+                  });
 }
 
 // Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed
@@ -1468,10 +1436,10 @@ extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t 
                                           const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
                                           uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream) {
   if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
-  SigTrace t;
-  t.family = SigFamily::MLDSA;
-  t.mldsa.mu = mu, t.mldsa.ctilde = ctilde, t.mldsa.w1 = w1, t.mldsa.flags = flags;
-  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
+  const VerifyIo v{pk, msg, msg_off, sig, ctx_str, ctx_len, status};
+  SigAlg a;
+  if (const int r = sig_args(ctx, alg, SIG_MLDSA, false, ctx_len, n, v.set(), a)) return r < 0 ? -1 : 0;
+  return mldsa_verify_rows(ctx, a, n, v, MldsaTrace{mu, ctilde, w1, flags}, (hipStream_t)stream);
 }
 
 // Tests only (not in qrkem.h): qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name that also writes, per row,
@@ -1484,10 +1452,10 @@ extern "C" int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t
                                            const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* digest,
                                            uint8_t* fors_pk, uint8_t* roots, uint32_t* flags, void* stream) {
   if (n && (!digest || !fors_pk || !roots || !flags)) return fail("null trace buffer");
-  SigTrace t;
-  t.family = SigFamily::SLHDSA;
-  t.slhdsa.digest = digest, t.slhdsa.fors_pk = fors_pk, t.slhdsa.roots = roots, t.slhdsa.flags = flags;
-  return sig_verify(ctx, alg, n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, t, stream);
+  const VerifyIo v{pk, msg, msg_off, sig, ctx_str, ctx_len, status};
+  SigAlg a;
+  if (const int r = sig_args(ctx, alg, SIG_SLHDSA, false, ctx_len, n, v.set(), a)) return r < 0 ? -1 : 0;
+  return slhdsa_verify_rows(ctx, a, n, v, SlhdsaTrace{digest, fors_pk, roots, flags}, (hipStream_t)stream);
 }
 
 // Tests only (not in qrkem.h): qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes, per

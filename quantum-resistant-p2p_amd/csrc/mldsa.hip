@@ -328,9 +328,14 @@ int mldsa_find(const char* name) {
   return -1;
 }
 
-void mldsa_sizes(int which, size_t out[4]) {
+SigSizes mldsa_sizes(int which) {
   const mldsa::Params& P = mldsa::params_of(which);
-  out[0] = P.pk, out[1] = P.sk, out[2] = P.sig, out[3] = P.w1_bytes();
+  return {(size_t)P.pk, (size_t)P.sk, (size_t)P.sig, 0};
+}
+
+MldsaTrace mldsa_trace_at(int which, const MldsaTrace& t, size_t row) {
+  if (!t.flags) return t;
+  return {t.mu + row * 64, t.ctilde + row * 64, t.w1 + row * mldsa::params_of(which).w1_bytes(), t.flags + row};
 }
 
 size_t mldsa_scratch_bytes(int which, size_t chunk) {
@@ -342,12 +347,9 @@ hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* m
                         const MldsaTrace& trace, void* scratch, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (ctx_len > 255 || n > (1u << 24)) return hipErrorInvalidValue;  // grids of n and n k l / 64 workgroups
-  switch (which) {
-    case 0: return mldsa::run<0>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 1: return mldsa::run<1>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 2: return mldsa::run<2>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-  }
-  return hipErrorInvalidValue;
+  return with_which<3>(which, [&](auto ps) {
+    return mldsa::run<decltype(ps)::value>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
+  });
 }
 
 }  // namespace qrk

@@ -1,11 +1,13 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
-// launchers (mlkem.hip, frodo.hip, util.hip).  Not part of the public ABI.
+// launchers (mlkem.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
+// mldsa.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace qrk {
 
@@ -37,7 +39,7 @@ extern thread_local KernelTimer* g_timer;
 // later successful API call, so a failed launch followed by successful ones would otherwise go
 // unnoticed).  The one error channel of the launchers: QRK_LAUNCH and qrk_chk record into it, every
 // launcher returns launch_status(), and only launch_begin() clears it.  An ABI call (abi.cpp: its
-// CallScope, and run_batch / sig_verify before each chunk) calls launch_begin() before it launches.
+// CallScope, and run_batch / run_rows before each chunk) calls launch_begin() before it launches.
 // A launcher's return value is therefore the answer and there is no merge step for an entry point
 // to forget; the one thing left to forget is launch_begin(), and that reports an earlier call's
 // failure loudly instead of losing this call's.
@@ -211,11 +213,25 @@ hipError_t dbg_poly1305(size_t n, const uint8_t* key32, const uint8_t* msg, cons
 hipError_t dbg_ghash(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                      hipStream_t st);
 
+// A signature launcher's parameter-set index as a compile-time constant: f(std::integral_constant<int, W>{}) for
+// the W < N that equals `which`, hipErrorInvalidValue for any other value.
+template <int N, class F>
+inline hipError_t with_which(int which, F&& f) {
+  if constexpr (N == 0) return hipErrorInvalidValue;
+  else return which == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_which<N - 1>(which, f);
+}
+
+// Bytes per row of a signature parameter set; n: the hash-based family's n (seeds 3 n, opt_rand n), 0 for ML-DSA.
+struct SigSizes {
+  size_t pk, sk, sig, n;
+};
+
 // ML-DSA.Verify over n rows of one chunk (mldsa.hip; FIPS 204, pure ML-DSA).  which = mldsa_find(name):
 // 0, 1, 2 for ML-DSA-44 / 65 / 87, -1 for any other name.  pk [n][pk], sig [n][sig], messages ragged
 // (msg + n + 1 offsets), one context string of ctx_len <= 255 bytes for all rows (device pointer; not
 // read when ctx_len = 0).  status[i] = 0 (valid) or -1, written for every row.  The trace pointers are
-// all set or all NULL (tests): mu [n][64] and ctilde [n][64] 8-byte aligned, w1 [n][w1 bytes], flags [n].
+// all set or all NULL (tests): mu [n][64] and ctilde [n][64] 8-byte aligned, w1 [n][w1 bytes], flags [n];
+// mldsa_trace_at gives the same trace `row` rows further on.
 struct MldsaTrace {
   uint8_t* mu = nullptr;
   uint8_t* ctilde = nullptr;
@@ -223,7 +239,8 @@ struct MldsaTrace {
   uint32_t* flags = nullptr;
 };
 int mldsa_find(const char* name);
-void mldsa_sizes(int which, size_t out[4]);  // pk, sk, sig, w1Encode bytes
+SigSizes mldsa_sizes(int which);
+MldsaTrace mldsa_trace_at(int which, const MldsaTrace& t, size_t row);
 size_t mldsa_scratch_bytes(int which, size_t chunk);
 hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* msg, const uint64_t* msg_off,
                         const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
@@ -233,7 +250,7 @@ hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* m
 // slhdsa_find(name): 2 set + flavour (set 0, 1, 2 = 128f, 192f, 256f; flavour 0 = "SPHINCS+-SHA2-*f-simple",
 // round 3.1; 1 = "SLH-DSA-SHA2-*f", FIPS 205), -1 for any other name.  Arguments as mldsa_verify; a context
 // string exists only in the FIPS 205 flavour.  The trace pointers are all set or all NULL (tests):
-// digest [n][m], fors_pk [n][n], roots [n][d][n], flags [n].
+// digest [n][m], fors_pk [n][n], roots [n][d][n], flags [n]; slhdsa_trace_at as mldsa_trace_at.
 struct SlhdsaTrace {
   uint8_t* digest = nullptr;
   uint8_t* fors_pk = nullptr;
@@ -242,7 +259,8 @@ struct SlhdsaTrace {
 };
 int slhdsa_find(const char* name);
 bool slhdsa_is_fips(int which);
-void slhdsa_sizes(int which, size_t out[6]);  // pk, sk, sig, m (digest bytes), n, d
+SigSizes slhdsa_sizes(int which);
+SlhdsaTrace slhdsa_trace_at(int which, const SlhdsaTrace& t, size_t row);
 size_t slhdsa_scratch_bytes(int which, size_t chunk);
 hipError_t slhdsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* msg, const uint64_t* msg_off,
                          const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,

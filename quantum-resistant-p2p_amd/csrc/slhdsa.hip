@@ -46,12 +46,12 @@ __global__ __launch_bounds__(64) void k_slhdsa_front(size_t n, const uint8_t* __
   constexpr Params P = make(PS);
   const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (row >= n) return;
-  const uint64_t o0 = off[row], o1 = off[row + 1];
-  if (o1 < o0 || o1 - o0 >= (1ull << 31)) {
+  uint64_t o0;
+  uint32_t mlen;
+  if (!row_span(off, row, o0, mlen)) {
     flags[row] = FLAG_LONG;
     return;
   }
-  const uint32_t mlen = (uint32_t)(o1 - o0);
   h_msg<PS>(sig + row * P.sig(), pk + row * P.pk(), msg + o0, mlen, ctx, ctx_len, digest + row * P.m);
   flags[row] = 0;
 }
@@ -86,26 +86,10 @@ __global__ __launch_bounds__(256) void k_slhdsa_core(size_t n, const uint8_t* __
   const uint8_t* sg = sig + row * P.sig();
   const uint8_t* dg = digest + row * P.m;
 
-  Seeds<N> sd;
-  {
-    uint32_t w[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) w[t] = t < NW ? be32(pkr + 4 * t) : 0u;
-    sd.s256 = sha::init();
-    sha::compress(sd.s256, w);
-    if constexpr (N > 16) {
-      uint64_t v[16];
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = t < NW / 2 ? ((uint64_t)w[2 * t] << 32) | w[2 * t + 1] : 0ull;
-      sd.s512 = sha::init512();
-      sha::compress512(sd.s512, v);
-    }
-  }
-
-  // md | idx_tree (8 bytes, big-endian, mod 2^(h - h')) | idx_leaf (1 byte, mod 2^h')
-  uint64_t tree = ((uint64_t)be32(dg + P.md()) << 32) | be32(dg + P.md() + 4);
-  if constexpr (P.h - P.hp < 64) tree &= (1ull << (P.h - P.hp)) - 1;  // 256f: all 64 bits, no shift by 64
-  uint32_t leaf = dg[P.md() + 8] & ((1u << P.hp) - 1);
+  const Seeds<N> sd = seed_states<N>(pkr);
+  uint64_t tree;
+  uint32_t leaf;
+  digest_indices<PS>(dg, tree, leaf);
 
   // ---- FORS: lane i < k reconstructs root i
   if (lane < P.k) {
@@ -135,21 +119,16 @@ __global__ __launch_bounds__(256) void k_slhdsa_core(size_t n, const uint8_t* __
   const uint8_t* xs = sg + N + P.fors_bytes();
 #pragma unroll 1
   for (int layer = 0; layer < P.d; ++layer, xs += P.xmss_bytes()) {
-    uint32_t csum = 0;  // sum of 15 - digit over the 2 n message digits, below 2^12
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) csum += 15 - ((node[j] >> (4 * q)) & 15);
-    }
+    const uint32_t csum = wots_csum<N>(node);
     for (int c = lane; c < LEN; c += 64) {
       uint32_t digit;
       if (c < P.len1()) {
-        uint32_t wsel = 0;
+        uint32_t wsel = 0;  // node[c >> 3], from registers
 #pragma unroll
         for (int j = 0; j < NW; ++j) wsel = (c >> 3) == j ? node[j] : wsel;
-        digit = (wsel >> (28 - 4 * (c & 7))) & 15;
+        digit = wots_msg_digit(c, wsel);
       } else {
-        digit = (csum >> (4 * (LEN - 1 - c))) & 15;
+        digit = wots_csum_digit<N>(c, csum);
       }
       uint32_t x[NW];
       load_node<N>(xs + (size_t)c * N, x);
@@ -174,8 +153,7 @@ __global__ __launch_bounds__(256) void k_slhdsa_core(size_t n, const uint8_t* __
       hash_h<N>(sd, Adrs{(uint32_t)layer, tree, TREE, 0, (uint32_t)j + 1, leaf >> (j + 1)}, node, au, (leaf >> j) & 1);
     }
     if (TRACE && lane == 0) store_node<N>(tr.roots + (row * P.d + layer) * N, node);
-    leaf = (uint32_t)tree & ((1u << P.hp) - 1);
-    tree >>= P.hp;
+    next_layer<PS>(tree, leaf);
   }
 
   uint32_t diff = 0;
@@ -233,9 +211,15 @@ int slhdsa_find(const char* name) {
 
 bool slhdsa_is_fips(int which) { return which & 1; }
 
-void slhdsa_sizes(int which, size_t out[6]) {
+SigSizes slhdsa_sizes(int which) {
   const slhdsa::Params P = slhdsa::make(which);
-  out[0] = P.pk(), out[1] = P.sk(), out[2] = P.sig(), out[3] = P.m, out[4] = P.n, out[5] = P.d;
+  return {(size_t)P.pk(), (size_t)P.sk(), (size_t)P.sig(), (size_t)P.n};
+}
+
+SlhdsaTrace slhdsa_trace_at(int which, const SlhdsaTrace& t, size_t row) {
+  const slhdsa::Params P = slhdsa::make(which);
+  if (!t.flags) return t;
+  return {t.digest + row * P.m, t.fors_pk + row * P.n, t.roots + row * P.d * P.n, t.flags + row};
 }
 
 size_t slhdsa_scratch_bytes(int which, size_t chunk) {
@@ -247,15 +231,9 @@ hipError_t slhdsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* 
                          const SlhdsaTrace& trace, void* scratch, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (ctx_len > 255 || (ctx_len && !slhdsa_is_fips(which)) || n > (1u << 24)) return hipErrorInvalidValue;
-  switch (which) {
-    case 0: return slhdsa::run<0>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 1: return slhdsa::run<1>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 2: return slhdsa::run<2>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 3: return slhdsa::run<3>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 4: return slhdsa::run<4>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-    case 5: return slhdsa::run<5>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
-  }
-  return hipErrorInvalidValue;
+  return with_which<6>(which, [&](auto ps) {
+    return slhdsa::run<decltype(ps)::value>(n, pk, msg, msg_off, sig, ctx_str, ctx_len, status, trace, scratch, st);
+  });
 }
 
 }  // namespace qrk

@@ -1,8 +1,8 @@
 // Device helpers shared by SLH-DSA-SHA2 / SPHINCS+-SHA2-simple verification (slhdsa.hip) and key generation
-// and signing (slhdsa_sign.hip): the parameter sets, the compressed address, the seeded-state tweakable hashes
-// F / H / T_l, H_msg, the LDS node stream and the FORS index extraction.  Everything here works on public
-// data or is constant-time in its inputs (the SHA-2 rounds); PRF(PK.seed, SK.seed, ADRS) has F's shape and is
-// hash_f on SK.seed with a PRF-type address.
+// and signing (slhdsa_sign.hip): the parameter sets, the compressed address, the PK.seed states and the tweakable
+// hashes F / H / T_l seeded with them, H_msg, the LDS node stream, a digest's FORS, tree and leaf indices and the
+// WOTS+ digits.  Everything here works on public data or is constant-time in its inputs (the SHA-2 rounds);
+// PRF(PK.seed, SK.seed, ADRS) has F's shape and is hash_f on SK.seed with a PRF-type address.
 #pragma once
 #include "qrkem_internal.h"
 #include "sha2.cuh"
@@ -35,6 +35,15 @@ constexpr Params make(int which) {
 
 __device__ __forceinline__ uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+
+// Start and length of ragged row `row`; false (FLAG_LONG) for decreasing offsets or 2^31 bytes or more.
+__device__ __forceinline__ bool row_span(const uint64_t* off, size_t row, uint64_t& o0, uint32_t& mlen) {
+  o0 = off[row];
+  const uint64_t o1 = off[row + 1];
+  if (o1 < o0 || o1 - o0 >= (1ull << 31)) return false;
+  mlen = (uint32_t)(o1 - o0);
+  return true;
 }
 
 // Byte q of M' (FIPS 205 Algorithm 22 / 24: M' = 0 || len(ctx) || ctx || M; round 3.1: M itself).
@@ -152,6 +161,36 @@ struct Seeds {  // the states after the PK.seed block
   sha::H8 s256;
   sha::H8x64 s512;  // n > 16 only
 };
+// ... computed from w = PK.seed || 0^(64 - n) as big-endian words: SHA-256 after w, and for n > 16 SHA-512 after
+// PK.seed || 0^(128 - n).  In parts, so that a caller that only stores them (slhdsa_sign.hip) holds one at a time.
+template <int N>
+__device__ __forceinline__ void seed_block(const uint8_t* pk_seed, uint32_t w[16]) {
+#pragma unroll
+  for (int t = 0; t < 16; ++t) w[t] = t < N / 4 ? be32(pk_seed + 4 * t) : 0u;
+}
+__device__ __forceinline__ sha::H8 seed_state256(const uint32_t w[16]) {
+  sha::H8 s = sha::init();
+  sha::compress(s, w);
+  return s;
+}
+template <int N>
+__device__ __forceinline__ sha::H8x64 seed_state512(const uint32_t w[16]) {
+  uint64_t v[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) v[t] = t < N / 8 ? ((uint64_t)w[2 * t] << 32) | w[2 * t + 1] : 0ull;
+  sha::H8x64 s = sha::init512();
+  sha::compress512(s, v);
+  return s;
+}
+template <int N>
+__device__ __forceinline__ Seeds<N> seed_states(const uint8_t* pk_seed) {
+  Seeds<N> sd;
+  uint32_t w[16];
+  seed_block<N>(pk_seed, w);
+  sd.s256 = seed_state256(w);
+  if constexpr (N > 16) sd.s512 = seed_state512<N>(w);
+  return sd;
+}
 
 // x = F(PK.seed, ADRS, x) = Trunc_n(SHA-256(PK.seed || 0^(64 - n) || ADRSc || x)): one compression.
 template <int N>
@@ -305,6 +344,40 @@ __device__ __forceinline__ uint32_t fors_index(const uint8_t* md, int i) {
       idx |= ((md[pos >> 3] >> (pos & 7)) & 1u) << j;
   }
   return idx;
+}
+
+// md | idx_tree (8 bytes, big-endian, mod 2^(h - h')) | idx_leaf (1 byte, mod 2^h'): the indices of layer 0
+template <int PS>
+__device__ __forceinline__ void digest_indices(const uint8_t* dg, uint64_t& tree, uint32_t& leaf) {
+  constexpr Params P = make(PS);
+  tree = ((uint64_t)be32(dg + P.md()) << 32) | be32(dg + P.md() + 4);
+  if constexpr (P.h - P.hp < 64) tree &= (1ull << (P.h - P.hp)) - 1;  // 256f: all 64 bits, no shift by 64
+  leaf = dg[P.md() + 8] & ((1u << P.hp) - 1);
+}
+// ... and from those of one hypertree layer the next one's: h' bits at a time, never a shift by 64
+template <int PS>
+__device__ __forceinline__ void next_layer(uint64_t& tree, uint32_t& leaf) {
+  constexpr Params P = make(PS);
+  leaf = (uint32_t)tree & ((1u << P.hp) - 1);
+  tree >>= P.hp;
+}
+
+// WOTS+ (lg_w = 4) over a node: the checksum, sum of 15 - digit over the 2 n message digits (below 2^12), and the
+// digit of chain c: for c < 2 n from `word`, the node's word c >> 3, for the other three from the checksum.
+template <int N>
+__device__ __forceinline__ uint32_t wots_csum(const uint32_t* node) {
+  uint32_t csum = 0;
+#pragma unroll
+  for (int j = 0; j < N / 4; ++j) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) csum += 15 - ((node[j] >> (4 * q)) & 15);
+  }
+  return csum;
+}
+__device__ __forceinline__ uint32_t wots_msg_digit(uint32_t c, uint32_t word) { return (word >> (28 - 4 * (c & 7))) & 15; }
+template <int N>
+__device__ __forceinline__ uint32_t wots_csum_digit(uint32_t c, uint32_t csum) {
+  return (csum >> (4 * (2 * N + 2 - c))) & 15;
 }
 
 }  // namespace slhdsa

@@ -84,20 +84,13 @@ constexpr int wots_threads(int ps) { return round64((make(ps).d * make(ps).len()
 
 template <int N>
 __device__ __forceinline__ void store_seeds(const uint8_t* pk_seed, const SignLayout& l, size_t row) {
-  constexpr int NW = N / 4;
   uint32_t w[16];
-#pragma unroll
-  for (int t = 0; t < 16; ++t) w[t] = t < NW ? be32(pk_seed + 4 * t) : 0u;
-  sha::H8 s = sha::init();
-  sha::compress(s, w);
+  seed_block<N>(pk_seed, w);
+  const sha::H8 s = seed_state256(w);  // stored before the next is made: one state in registers at a time
 #pragma unroll
   for (int t = 0; t < 8; ++t) l.s256[row * 8 + t] = s.h[t];
   if constexpr (N > 16) {
-    uint64_t v[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = t < NW / 2 ? ((uint64_t)w[2 * t] << 32) | w[2 * t + 1] : 0ull;
-    sha::H8x64 b = sha::init512();
-    sha::compress512(b, v);
+    const sha::H8x64 b = seed_state512<N>(w);
 #pragma unroll
     for (int t = 0; t < 8; ++t) l.s512[row * 8 + t] = b.h[t];
   }
@@ -114,23 +107,11 @@ __device__ __forceinline__ Seeds<N> load_seeds(const SignLayout& l, size_t row) 
   return sd;
 }
 
-// md | idx_tree (8 bytes, big-endian, mod 2^(h - h')) | idx_leaf (1 byte, mod 2^h'), as the verify core
-template <int PS>
-__device__ __forceinline__ void digest_indices(const uint8_t* dg, uint64_t& tree, uint32_t& leaf) {
-  constexpr Params P = make(PS);
-  tree = ((uint64_t)be32(dg + P.md()) << 32) | be32(dg + P.md() + 4);
-  if constexpr (P.h - P.hp < 64) tree &= (1ull << (P.h - P.hp)) - 1;  // 256f: all 64 bits, no shift by 64
-  leaf = dg[P.md() + 8] & ((1u << P.hp) - 1);
-}
-// ... and those of hypertree layer `layer`: h' bits at a time, never a shift by 64
+// The indices of hypertree layer `layer` from those of layer 0 (digest_indices).
 template <int PS>
 __device__ __forceinline__ void layer_indices(int layer, uint64_t& tree, uint32_t& leaf) {
-  constexpr Params P = make(PS);
 #pragma unroll 1
-  for (int q = 0; q < layer; ++q) {
-    leaf = (uint32_t)tree & ((1u << P.hp) - 1);
-    tree >>= P.hp;
-  }
+  for (int q = 0; q < layer; ++q) next_layer<PS>(tree, leaf);
 }
 
 // ------------------------------------------------------------------ R, H_msg, the PK.seed states
@@ -146,12 +127,12 @@ __global__ __launch_bounds__(64) void k_slhsign_front(size_t n, const uint8_t* _
   constexpr uint32_t N = P.n, NW = N / 4;
   const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (row >= n) return;
-  const uint64_t o0 = off[row], o1 = off[row + 1];
-  if (o1 < o0 || o1 - o0 >= (1ull << 31)) {
+  uint64_t o0;
+  uint32_t mlen;
+  if (!row_span(off, row, o0, mlen)) {
     l.flags[row] = FLAG_LONG;
     return;
   }
-  const uint32_t mlen = (uint32_t)(o1 - o0);
   const uint32_t pre = P.fips ? 2 + ctx_len : 0;
   const uint8_t* prf = sk + row * P.sk() + N;       // SK.prf
   const uint8_t* pkr = sk + row * P.sk() + 2 * N;   // PK.seed || PK.root
@@ -366,15 +347,7 @@ __global__ __launch_bounds__(wots_threads(PS)) void k_slhsign_wots(const uint8_t
   for (uint32_t t = tid; t < (uint32_t)((P.d - 1) * NW); t += THREADS)  // layer j signs root j - 1
     msgs[NW + t] = be32(l.roots + row * P.d * N + 4 * t);
   __syncthreads();
-  if (tid < (uint32_t)P.d) {  // sum of 15 - digit over the 2 n message digits, below 2^12
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += 15 - ((msgs[tid * NW + j] >> (4 * q)) & 15);
-    }
-    csum[tid] = s;
-  }
+  if (tid < (uint32_t)P.d) csum[tid] = wots_csum<N>(msgs + tid * NW);
   __syncthreads();
 
   uint32_t seed[NW];
@@ -382,8 +355,8 @@ __global__ __launch_bounds__(wots_threads(PS)) void k_slhsign_wots(const uint8_t
 #pragma unroll 1
   for (uint32_t it = tid; it < (uint32_t)(P.d * LEN); it += THREADS) {
     const uint32_t layer = it / LEN, c = it % LEN;
-    const uint32_t digit = c < (uint32_t)P.len1() ? (msgs[layer * NW + (c >> 3)] >> (28 - 4 * (c & 7))) & 15
-                                                   : (csum[layer] >> (4 * (LEN - 1 - c))) & 15;
+    const uint32_t digit = c < (uint32_t)P.len1() ? wots_msg_digit(c, msgs[layer * NW + (c >> 3)])  // from LDS
+                                                   : wots_csum_digit<N>(c, csum[layer]);
     uint64_t tree = tree0;
     uint32_t leaf = leaf0;
     layer_indices<PS>((int)layer, tree, leaf);
@@ -459,12 +432,9 @@ hipError_t slhdsa_keypair(int which, size_t n, const uint8_t* seeds, uint8_t* pk
                           hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (n > SLHDSA_SIGN_MAX_ROWS) return hipErrorInvalidValue;
-  switch (which) {
-    case 0: case 1: return slhdsa::run_keypair<0>(n, seeds, pk, sk, scratch, st);  // Algorithm 18 has no flavour
-    case 2: case 3: return slhdsa::run_keypair<2>(n, seeds, pk, sk, scratch, st);
-    case 4: case 5: return slhdsa::run_keypair<4>(n, seeds, pk, sk, scratch, st);
-  }
-  return hipErrorInvalidValue;
+  return with_which<6>(which, [&](auto ps) {  // Algorithm 18 has no flavour
+    return slhdsa::run_keypair<decltype(ps)::value & ~1>(n, seeds, pk, sk, scratch, st);
+  });
 }
 
 hipError_t slhdsa_sign(int which, size_t n, const uint8_t* sk, const uint8_t* msg, const uint64_t* msg_off,
@@ -472,15 +442,10 @@ hipError_t slhdsa_sign(int which, size_t n, const uint8_t* sk, const uint8_t* ms
                        void* scratch, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (ctx_len > 255 || (ctx_len && !slhdsa_is_fips(which)) || n > SLHDSA_SIGN_MAX_ROWS) return hipErrorInvalidValue;
-  switch (which) {
-    case 0: return slhdsa::run_sign<0>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-    case 1: return slhdsa::run_sign<1>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-    case 2: return slhdsa::run_sign<2>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-    case 3: return slhdsa::run_sign<3>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-    case 4: return slhdsa::run_sign<4>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-    case 5: return slhdsa::run_sign<5>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch, st);
-  }
-  return hipErrorInvalidValue;
+  return with_which<6>(which, [&](auto ps) {
+    return slhdsa::run_sign<decltype(ps)::value>(n, sk, msg, msg_off, opt_rand, ctx_str, ctx_len, sig, status, scratch,
+                                                 st);
+  });
 }
 
 }  // namespace qrk

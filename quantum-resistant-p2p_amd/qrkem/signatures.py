@@ -100,6 +100,23 @@ class _BatchVerifier(SignatureAlgorithm):
         except Exception:
             pass
 
+    def _stream(self):
+        return ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ragged(self, messages, offsets):
+        """``(messages, offsets)`` as the batch methods accept them -> the validated device tensors and n."""
+        if offsets is None:
+            data, off = pack_infos([bytes(m) for m in messages])
+            messages, offsets = _dev(data, self.device), _dev(off.view(np.int64), self.device)
+        n = offsets.numel() - 1
+        if not (_is_dev(messages) and messages.dtype == torch.uint8 and messages.dim() == 1 and
+                messages.is_contiguous()):
+            raise ValueError("messages must be a contiguous 1-D uint8 device tensor")
+        if not (_is_dev(offsets) and offsets.dtype in (torch.int64, torch.uint64) and offsets.dim() == 1 and
+                n >= 0 and offsets.is_contiguous()):
+            raise ValueError("offsets must be a contiguous 64-bit device tensor of n + 1 entries")
+        return messages, offsets, n
+
     # ------------------------------------------------------------------ the reference's single calls
     def generate_keypair(self) -> Tuple[bytes, bytes]:
         raise NotImplementedError(self.VERIFY_ONLY.format("key generation"))
@@ -132,16 +149,7 @@ class _BatchVerifier(SignatureAlgorithm):
     def verify_status(self, public_keys, messages, signatures, offsets=None):
         """As :meth:`verify_batch`, returning the int32 [n] device tensor of the C ABI: 0 valid, -1 not."""
         ctx = self._context()  # first: without a device this is the error to raise
-        if offsets is None:
-            data, off = pack_infos([bytes(m) for m in messages])
-            messages, offsets = _dev(data, self.device), _dev(off.view(np.int64), self.device)
-        n = offsets.numel() - 1
-        if not (_is_dev(messages) and messages.dtype == torch.uint8 and messages.dim() == 1 and
-                messages.is_contiguous()):
-            raise ValueError("messages must be a contiguous 1-D uint8 device tensor")
-        if not (_is_dev(offsets) and offsets.dtype in (torch.int64, torch.uint64) and offsets.dim() == 1 and
-                n >= 0 and offsets.is_contiguous()):
-            raise ValueError("offsets must be a contiguous 64-bit device tensor of n + 1 entries")
+        messages, offsets, n = self._ragged(messages, offsets)
         if not _is_dev(public_keys):
             public_keys = _dev(_as_host(public_keys, self.public_key_size), self.device)
         if not _is_dev(signatures):
@@ -150,8 +158,7 @@ class _BatchVerifier(SignatureAlgorithm):
         _check_dev(signatures, self.signature_size, f"{self.FAMILY} signatures", n)
         status = torch.empty((n,), dtype=torch.int32, device=messages.device)
         rc = LIB.qrk_sig_verify_batch(ctx, self.variant.encode(), n, _ptr(public_keys), _ptr(messages), _ptr(offsets),
-                                      _ptr(signatures), None, 0, _ptr(status),
-                                      ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+                                      _ptr(signatures), None, 0, _ptr(status), self._stream())
         if rc != 0:
             raise RuntimeError(f"qrkem {self.FAMILY} verify failed ({self.variant}): {last_error()}")
         return status
@@ -211,9 +218,6 @@ class SPHINCSSignature(_BatchVerifier):
         self.n_bytes = self.public_key_size // 2
 
     # ------------------------------------------------------------------ key generation and signing (signing=True)
-    def _stream(self):
-        return ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def generate_keypair(self) -> Tuple[bytes, bytes]:
         """(public key, secret key) from 3 n fresh bytes of the OS CSPRNG (signatures.py:238-259)."""
         if not self.signing:
@@ -264,16 +268,7 @@ class SPHINCSSignature(_BatchVerifier):
         if not self.signing:
             return super().sign(b"", b"")
         ctx = self._context()
-        if offsets is None:
-            data, off = pack_infos([bytes(m) for m in messages])
-            messages, offsets = _dev(data, self.device), _dev(off.view(np.int64), self.device)
-        n = offsets.numel() - 1
-        if not (_is_dev(messages) and messages.dtype == torch.uint8 and messages.dim() == 1 and
-                messages.is_contiguous()):
-            raise ValueError("messages must be a contiguous 1-D uint8 device tensor")
-        if not (_is_dev(offsets) and offsets.dtype in (torch.int64, torch.uint64) and offsets.dim() == 1 and
-                n >= 0 and offsets.is_contiguous()):
-            raise ValueError("offsets must be a contiguous 64-bit device tensor of n + 1 entries")
+        messages, offsets, n = self._ragged(messages, offsets)
         if not _is_dev(private_keys):
             private_keys = _dev(_as_host(private_keys, self.secret_key_size), self.device)
         _check_dev(private_keys, self.secret_key_size, f"{self.FAMILY} secret keys", n)

@@ -18,6 +18,7 @@ for a handshake whose HKDF or key comparison was rejected): the launchers' own r
 see the failure, and those entry points never looked at the channel.  That is the defect pinned here.
 """
 import ctypes as ct
+import functools
 
 import numpy as np
 import pytest
@@ -239,6 +240,57 @@ def sig_verify(lib, ctx):
                                             sig.data_ptr(), None, 0, st.data_ptr(), _stream()), [st]
 
 
+SLH, SLH_ROWS = "SLH-DSA-SHA2-128f", 2  # the cheapest set; one partly filled front workgroup, one core workgroup
+
+
+@functools.lru_cache(maxsize=None)
+def _slh_gold():
+    """tests/golden/slhdsa.json, loaded once for the three cases (the load rebuilds every key with the spec)."""
+    import make_golden_slhdsa as gold
+    return gold, gold.load()[SLH]
+
+
+def _slh_fixture():
+    """The key of tests/golden/slhdsa.json and its first SLH_ROWS messages (0 and 8 bytes), ragged."""
+    gold, f = _slh_gold()
+    msgs = f["msgs"][:SLH_ROWS]
+    msg = _dev(np.frombuffer(b"".join(msgs), np.uint8))
+    off = _dev(np.cumsum([0] + [len(m) for m in msgs]).astype(np.uint64).view(np.int64))
+    return gold, f, msg, off
+
+
+def slh_verify(lib, ctx):
+    gold, f, msg, off = _slh_fixture()
+    n = SLH_ROWS
+    sigs = gold.signatures(SLH, {**f, "msgs": f["msgs"][:n], "records": f["records"][:n]})
+    pk = _dev(np.frombuffer(f["pk"] * n, np.uint8))
+    sig = _dev(np.frombuffer(b"".join(sigs), np.uint8))
+    st = _out(n, dtype=torch.int32)
+    return lambda: lib.qrk_sig_verify_batch(ctx, SLH.encode(), n, pk.data_ptr(), msg.data_ptr(), off.data_ptr(),
+                                            sig.data_ptr(), None, 0, st.data_ptr(), _stream()), [st]
+
+
+def slh_keypair(lib, ctx):
+    gold, f, _, _ = _slh_fixture()
+    n = SLH_ROWS
+    seeds = np.frombuffer(b"".join(f["seeds"]), np.uint8)  # row 0: the fixture key; the rest: fixed random seeds
+    seeds = _dev(np.stack([seeds] + [_rand(81 + i, seeds.size) for i in range(1, n)]))
+    pk, sk = _out(n, len(f["pk"])), _out(n, len(f["sk"]))
+    return lambda: lib.qrk_sig_keypair_batch(ctx, SLH.encode(), n, seeds.data_ptr(), pk.data_ptr(), sk.data_ptr(),
+                                             _stream()), [pk, sk]
+
+
+def slh_sign(lib, ctx):
+    gold, f, msg, off = _slh_fixture()
+    n = SLH_ROWS
+    sk = _dev(np.frombuffer(f["sk"] * n, np.uint8))
+    size = (SZ * 3)()
+    assert lib.qrk_sig_sizes(SLH.encode(), size) == 0
+    sig, st = _out(n, size[2]), _out(n, dtype=torch.int32)
+    return lambda: lib.qrk_sig_sign_batch(ctx, SLH.encode(), n, sk.data_ptr(), msg.data_ptr(), off.data_ptr(), None,
+                                          None, 0, sig.data_ptr(), st.data_ptr(), _stream()), [sig, st]
+
+
 def frodo_decaps_trace(lib, ctx):
     alg, n = "FrodoKEM-640-SHAKE", 64
     s, _, _, _, sk, c = _kem_chain(lib, ctx, alg, n)
@@ -267,6 +319,8 @@ CASES.update({
     "base64_decode": base64_decode, "hqc_supports": hqc_supports, "hqc_code_decode": hqc_code_decode,
     "dbg_hqc_decaps_trace": hqc_decaps_trace,
     "bench_coins": bench_coins, "tamper": tamper, "sig_verify-ML-DSA-44": sig_verify,
+    f"sig_verify-{SLH}-{SLH_ROWS}": slh_verify, f"sig_keypair-{SLH}-{SLH_ROWS}": slh_keypair,
+    f"sig_sign-{SLH}-{SLH_ROWS}": slh_sign,
     "dbg_poly1305": dbg_hook("qrk_dbg_poly1305_batch", 32), "dbg_ghash": dbg_hook("qrk_dbg_ghash_batch", 16),
     "dbg_frodo_decaps_trace-FrodoKEM-640-SHAKE-64": frodo_decaps_trace,
 })
