@@ -82,12 +82,13 @@ OQS_STATUS OQS_KEM_encaps_derand(const OQS_KEM *kem, uint8_t *ciphertext, uint8_
                                  const uint8_t *public_key, const uint8_t *seed);
 
 /* Signature half of the liboqs ABI: the reference's oqs.py binds these at
- * import time (oqs.py:684-697).  The engine has no ML-DSA KeyGen or Sign, and
- * an OQS_SIG that could only verify would be a trap; the hash-based family,
- * which it can sign with, has no single-shot path here.  So the registry stays
- * empty (count 0) and every call here fails.  The batched calls of Part 2
- * verify for both families (qrk_sig_verify_batch) and generate keys and sign
- * for the hash-based one (qrk_sig_keypair_batch, qrk_sig_sign_batch). */
+ * import time (oqs.py:684-697).  Neither signature family has a single-shot
+ * path here, and a registry that listed names whose calls fail would be a
+ * trap.  So the registry stays empty (count 0) and every call here fails.
+ * The batched calls of Part 2 verify for both families
+ * (qrk_sig_verify_batch) and generate keys and sign: for the hash-based one
+ * qrk_sig_keypair_batch / qrk_sig_sign_batch, for ML-DSA
+ * qrk_mldsa_keypair_batch / qrk_mldsa_sign_batch. */
 typedef struct OQS_SIG OQS_SIG;
 size_t OQS_SIG_alg_count(void);
 const char *OQS_SIG_alg_identifier(size_t i);
@@ -272,9 +273,9 @@ int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
 /* ML-DSA signature verification (FIPS 204 final, "pure" ML-DSA: Verify, Algorithm 3), the step the
  * reference runs on every handshake and chat message (signatures.py:167 from messaging.py:721, 933,
  * 1174, 1480).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; any other name returns -1 with
- * qrk_last_error() set.  For ML-DSA verification only: there is no ML-DSA KeyGen or Sign (and the
- * OQS_SIG registry of Part 1 stays empty); the hash-based names below also have
- * qrk_sig_keypair_batch and qrk_sig_sign_batch.
+ * qrk_last_error() set.  ML-DSA KeyGen and Sign are qrk_mldsa_keypair_batch and qrk_mldsa_sign_batch
+ * below (the OQS_SIG registry of Part 1 stays empty); the hash-based names have qrk_sig_keypair_batch
+ * and qrk_sig_sign_batch, which refuse an ML-DSA name.
  * The same two calls verify hash-based signatures, the SHA2 "f" parameter sets, in two flavours:
  * "SPHINCS+-SHA2-128f-simple", "SPHINCS+-SHA2-192f-simple", "SPHINCS+-SHA2-256f-simple" (the round-3.1
  * submission as liboqs ships it, what the reference's SPHINCSSignature asks for, signatures.py:208-212)
@@ -300,7 +301,7 @@ int qrk_sig_verify_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t 
 /* SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" key generation and signing: the other half of the reference's
  * SPHINCSSignature (signatures.py:238-292; sign is called on every key-exchange message and chat message,
  * messaging.py:620, 864, 1090).  alg: the six hash-based names of qrk_sig_sizes.  An ML-DSA name returns -1
- * with a message naming it (qrkem has no ML-DSA KeyGen or Sign), any other name -1 "unsupported signature
+ * with a message naming it and qrk_mldsa_keypair_batch / qrk_mldsa_sign_batch, any other name -1 "unsupported signature
  * algorithm".  Checked before any device work, in this order: null context, name, ctx_len > 255, a context
  * under a "SPHINCS+-" name; then n == 0 returns 0.  Device pointers, stream-ordered on `stream`.  Output is
  * byte-exact FIPS 205 Algorithm 18 / 19 (and the round-3.1 submission's) for the given seeds and opt_rand.
@@ -321,6 +322,31 @@ int qrk_sig_keypair_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t
 int qrk_sig_sign_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *msg,
                        const uint64_t *msg_off, const uint8_t *opt_rand, const uint8_t *ctx_str, size_t ctx_len,
                        uint8_t *sig, int32_t *status, void *stream);
+
+/* ML-DSA key generation and signing (FIPS 204 final, "pure" ML-DSA: KeyGen_internal, Algorithm 6, and Sign,
+ * Algorithm 2 over Sign_internal, Algorithm 7): the other half of the reference's MLDSASignature, its default
+ * signature (signatures.py generate_keypair / sign; sign is called on every key-exchange and chat message,
+ * messaging.py:620, 864, 1090).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87".  A hash-based name returns -1 with
+ * a message naming it and qrk_sig_keypair_batch / qrk_sig_sign_batch, any other name -1 "unsupported signature
+ * algorithm".  Checked before any device work, in this order: null context, name, ctx_len > 255; then n == 0
+ * returns 0; then null buffers.  Device pointers, stream-ordered on `stream`.  Output is byte-exact FIPS 204 for
+ * the given xi and rnd.  Rows per launch follow qrk_ctx_set_chunk; the context's scratch grows on demand by
+ * 16452 / 30788 / 57412 bytes per row (ML-DSA-44 / 65 / 87) and holds public values only: A_hat = ExpandA(rho)
+ * (k l KiB), mu and a flag word.  xi, rho', K, rho'', s1, s2, t0 and the masks y are read from `xi` and `sk` into
+ * registers and on-chip memory, which is zeroed before a workgroup exits, and are never copied anywhere else.
+ *
+ * KeyGen: xi [n][32], the caller draws them; pk [n][pk bytes], sk [n][sk bytes] (the sizes of qrk_sig_sizes). */
+int qrk_mldsa_keypair_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *xi, uint8_t *pk, uint8_t *sk,
+                            void *stream);
+/* Sign: sk [n][sk bytes]; messages ragged and ctx_str / ctx_len as qrk_sig_verify_batch; rnd NULL = the
+ * deterministic variant (32 zero bytes), else [n][32] fresh random bytes per row (hedged); sig [n][sig bytes].
+ * status (required, int32[n]): 0, or -1 with an all-zero signature row for a row of 2^31 bytes or more, a row
+ * whose offsets decrease, a secret key with an s1 / s2 coefficient outside [-eta, eta], or a row whose rejection
+ * loop ran 814 iterations (the cap FIPS 204 Appendix C allows; about 2^-200 for an honest key) without an
+ * accepted signature; every row is written exactly once. */
+int qrk_mldsa_sign_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *msg,
+                         const uint64_t *msg_off, const uint8_t *rnd, const uint8_t *ctx_str, size_t ctx_len,
+                         uint8_t *sig, int32_t *status, void *stream);
 
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853

@@ -1339,15 +1339,20 @@ int qrk_sig_sizes(const char* alg, size_t out[3]) {
   return 0;
 }
 
-// The argument checks of every signature call in the order qrkem.h documents (a trace hook takes its own `family`
-// only, a signing call no ML-DSA name; `bufs`: no required pointer is null).  -1: failed, 1: n == 0, 0: go, `a` set.
+// The argument checks of every signature call in the order qrkem.h documents (a trace hook or a qrk_mldsa_* call
+// takes its own `family` only; of the signing calls the generic pair takes no ML-DSA name and the ML-DSA pair no
+// hash-based one, each naming the other; `bufs`: no required pointer is null).  -1: failed, 1: n == 0, 0: go, `a` set.
 static int sig_args(qrk_ctx* ctx, const char* alg, int family, bool signing, size_t ctx_len, size_t n, bool bufs,
                     SigAlg& a) {
   if (!ctx) return fail("null context");
   a = sig_find(alg);
+  if (signing && family == SIG_MLDSA && a.family == SIG_SLHDSA)
+    return fail(std::string(alg) + ": a hash-based parameter set: its KeyGen and Sign are qrk_sig_keypair_batch / "
+                                   "qrk_sig_sign_batch");
   if (a.family == SIG_ANY || (family != SIG_ANY && family != a.family)) return sig_unsupported(alg);
-  if (signing && a.family == SIG_MLDSA)
-    return fail(std::string(alg) + ": qrkem has no ML-DSA KeyGen or Sign (verification only; signing stays with liboqs)");
+  if (signing && family == SIG_ANY && a.family == SIG_MLDSA)
+    return fail(std::string(alg) + ": the generic signing calls have no ML-DSA KeyGen or Sign (they are "
+                                   "qrk_mldsa_keypair_batch / qrk_mldsa_sign_batch)");
   if (ctx_len > 255) return fail(a.family == SIG_MLDSA ? "ML-DSA context strings are at most 255 bytes"
                                                        : "SLH-DSA context strings are at most 255 bytes");
   if (a.family == SIG_SLHDSA && ctx_len && !slhdsa_is_fips(a.which))
@@ -1424,6 +1429,56 @@ int qrk_sig_sign_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* s
                                        opt_rand ? opt_rand + off * a.sz.n : nullptr, ctx_str, ctx_len, sig + off * a.sz.sig,
                                        status + off, ctx->scratch, st);
                   });
+}
+
+// ML-DSA key generation and signing (mldsa_sign.hip).  Chunks are capped like verification's: the scratch is
+// A_hat, k l KiB per row, plus 68 bytes.
+int qrk_mldsa_keypair_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* xi, uint8_t* pk, uint8_t* sk,
+                            void* stream) {
+  SigAlg a;
+  if (const int r = sig_args(ctx, alg, SIG_MLDSA, true, 0, n, xi && pk && sk, a)) return r < 0 ? -1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  return run_rows(ctx, st, n, verify_cap(mldsa_sign_scratch_bytes(a.which, 1)), mldsa_sign_scratch_bytes, a.which,
+                  "mldsa_keypair", [&](size_t off, size_t m) {
+                    return mldsa_keypair(a.which, m, xi + off * 32, pk + off * a.sz.pk, sk + off * a.sz.sk, ctx->scratch,
+                                         st);
+                  });
+}
+
+// qrk_mldsa_sign_batch and its traced twin qrk_dbg_mldsa_sign_trace (iters != NULL): one body
+static int mldsa_sign_call(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                           const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len,
+                           uint8_t* sig, int32_t* status, uint32_t max_iters, bool traced, uint8_t* mu, uint32_t* iters,
+                           hipStream_t st) {
+  SigAlg a;
+  const bool bufs = sk && msg && msg_off && sig && status && (ctx_str || !ctx_len) && (!traced || (mu && iters));
+  if (const int r = sig_args(ctx, alg, SIG_MLDSA, true, ctx_len, n, bufs, a)) return r < 0 ? -1 : 0;
+  return run_rows(ctx, st, n, verify_cap(mldsa_sign_scratch_bytes(a.which, 1)), mldsa_sign_scratch_bytes, a.which,
+                  "mldsa_sign", [&](size_t off, size_t m) {
+                    return mldsa_sign(a.which, m, sk + off * a.sz.sk, msg, msg_off + off, rnd ? rnd + off * 32 : nullptr,
+                                      ctx_str, ctx_len, sig + off * a.sz.sig, status + off, max_iters,
+                                      traced ? mu + off * 64 : nullptr, traced ? iters + off : nullptr, ctx->scratch, st);
+                  });
+}
+
+int qrk_mldsa_sign_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                         const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len,
+                         uint8_t* sig, int32_t* status, void* stream) {
+  return mldsa_sign_call(ctx, alg, n, sk, msg, msg_off, rnd, ctx_str, ctx_len, sig, status, MLDSA_SIGN_MAX_ITERS, false,
+                         nullptr, nullptr, (hipStream_t)stream);
+}
+
+// Tests only (not in qrkem.h): qrk_mldsa_sign_batch with the loop's cap as an argument, which also writes, per row,
+// mu [n][64] (zeros for a row refused for its offsets or length) and the iterations run, iters [n] (0 for a refused
+// row, max_iters for one that exhausted them).  The production kernel stores them itself, in an instantiation no
+// other call launches; this is what pins the rejection loop against tests/mldsa_spec.py iteration by iteration,
+// and what lets a test reach the cap.
+extern "C" int qrk_dbg_mldsa_sign_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                                        const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str,
+                                        size_t ctx_len, uint8_t* sig, int32_t* status, uint32_t max_iters, uint8_t* mu,
+                                        uint32_t* iters, void* stream) {
+  return mldsa_sign_call(ctx, alg, n, sk, msg, msg_off, rnd, ctx_str, ctx_len, sig, status, max_iters, true, mu, iters,
+                         (hipStream_t)stream);
 }
 
 // Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed

@@ -20,64 +20,11 @@
 // core kernel's workgroup at once).  Nothing here may be copied into a signing path.
 #include <cstring>
 
-#include "keccak.cuh"
-#include "mldsa_arith.cuh"
+#include "mldsa_common.cuh"
 #include "qrkem_internal.h"
 
 namespace qrk {
 namespace mldsa {
-
-template <int PS>
-struct Set;
-template <>
-struct Set<0> {
-  static constexpr Params P = P44;
-};
-template <>
-struct Set<1> {
-  static constexpr Params P = P65;
-};
-template <>
-struct Set<2> {
-  static constexpr Params P = P87;
-};
-
-// Absorbs the `len` bytes at(0) .. at(len - 1) into a sponge of RW rate words whose current block
-// already holds SW words, pads (SHAKE) and permutes: on return s holds the first output block.
-template <int RW, int SW, class At>
-__device__ __forceinline__ void absorb_bytes(KState& s, uint32_t len, At at) {
-  auto word = [&](uint32_t p) -> uint64_t {
-    uint64_t r = 0;
-    if (p + 8 <= len) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r |= (uint64_t)at(p + j) << (8 * j);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t i = p + j;
-        const uint32_t b = i < len ? at(i) : (i == len ? DS_SHAKE : 0u);
-        r |= (uint64_t)b << (8 * j);
-      }
-    }
-    return r;
-  };
-  uint32_t pos = 0;
-#pragma unroll
-  for (int w = SW; w < RW; ++w) {
-    kxor(s, w, word(pos));
-    pos += 8;
-  }
-  while (pos <= len) {  // the padding byte (stream index len) is not in yet
-    keccak_f(s);
-#pragma unroll
-    for (int w = 0; w < RW; ++w) {
-      kxor(s, w, word(pos));
-      pos += 8;
-    }
-  }
-  s.a[RW - 1].hi ^= 0x80000000u;
-  keccak_f(s);
-}
 
 template <int PS>
 __global__ __launch_bounds__(64) void k_mldsa_front(size_t n, const uint8_t* __restrict__ pk,
@@ -138,46 +85,8 @@ __global__ __launch_bounds__(64) void k_mldsa_front(size_t n, const uint8_t* __r
 template <int PS>
 __global__ __launch_bounds__(64) void k_mldsa_expand(size_t n, const uint8_t* __restrict__ pk,
                                                      int32_t* __restrict__ A) {
-  constexpr Params P = Set<PS>::P;
-  constexpr int KL = P.k * P.l, STRIDE = 57;
-  __shared__ int tile[64 * STRIDE];  // the coefficients each lane accepted from the current block (<= 56)
-  const int lane = threadIdx.x;
-  const size_t npoly = n * KL, first = (size_t)blockIdx.x * 64, gid = first + lane;
-  const size_t row = gid < npoly ? gid / KL : 0;
-  const int e = (int)(gid % KL), i = e / P.l, j = e % P.l;
-  const uint8_t* rho = pk + row * P.pk;
-  KState s;
-  kzero(s);
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) v |= (uint64_t)rho[8 * w + b] << (8 * b);
-    kxor(s, w, v);
-  }
-  // rho || column || row, then the SHAKE padding
-  s.a[4].lo ^= (uint32_t)j | ((uint32_t)i << 8) | (DS_SHAKE << 16);
-  s.a[RW_SHAKE128 - 1].hi ^= 0x80000000u;
-  int cnt = 0, written = 0;
-  rej_ntt_poly(
-      [&](uint64_t(&w)[21]) {
-        keccak_f(s);
-#pragma unroll
-        for (int x = 0; x < 21; ++x) w[x] = kword(s, x);
-      },
-      [&](int, int v) { tile[lane * STRIDE + cnt++] = v; },
-      [&](int) {
-        // Lane r's run goes out as one contiguous store of up to 56 lanes.  written + cnt <= 256, so
-        // every store stays inside polynomial first + r, and polynomials past npoly store nothing.
-        __syncthreads();
-        for (int r = 0; r < 64 && first + r < npoly; ++r) {
-          const int nr = __builtin_amdgcn_readlane(cnt, r), wr = __builtin_amdgcn_readlane(written, r);
-          if (lane < nr) A[(first + r) * N + wr + lane] = tile[r * STRIDE + lane];
-        }
-        written += cnt;
-        cnt = 0;
-        __syncthreads();
-      });
+  __shared__ int tile[64 * EXPAND_STRIDE];
+  expand_a_block<PS>(n, pk, Set<PS>::P.pk, A, tile);  // rho: the first 32 bytes of a public key
 }
 
 template <int PS>

@@ -1,6 +1,6 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
 // launchers (mlkem.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
-// mldsa.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
+// mldsa.hip, mldsa_sign.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -245,6 +245,20 @@ size_t mldsa_scratch_bytes(int which, size_t chunk);
 hipError_t mldsa_verify(int which, size_t n, const uint8_t* pk, const uint8_t* msg, const uint64_t* msg_off,
                         const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len, int32_t* status,
                         const MldsaTrace& trace, void* scratch, hipStream_t st);
+
+// ML-DSA.KeyGen and ML-DSA.Sign over n rows of one chunk (mldsa_sign.hip; FIPS 204 Algorithms 6 and 2 / 7); which
+// as above.  xi [n][32]; rnd NULL (deterministic: 32 zero bytes) or [n][32]; messages and context as mldsa_verify.
+// status[i] = 0, or -1 with an all-zero signature row (a row of 2^31 bytes or more, decreasing offsets, a secret
+// key with an s1 / s2 field outside [-eta, eta], or max_iters iterations without an accepted signature);
+// MLDSA_SIGN_MAX_ITERS in production.  trace_mu [n][64] and trace_iters [n] are both set or both NULL (tests).
+// The scratch holds public values only (mldsa_sign_scratch_bytes: A_hat, mu, a flag word: k l KiB + 68 bytes per row).
+constexpr uint32_t MLDSA_SIGN_MAX_ITERS = 814;  // FIPS 204 Appendix C: the least cap an implementation may set
+size_t mldsa_sign_scratch_bytes(int which, size_t chunk);
+hipError_t mldsa_keypair(int which, size_t n, const uint8_t* xi, uint8_t* pk, uint8_t* sk, void* scratch,
+                         hipStream_t st);
+hipError_t mldsa_sign(int which, size_t n, const uint8_t* sk, const uint8_t* msg, const uint64_t* msg_off,
+                      const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig, int32_t* status,
+                      uint32_t max_iters, uint8_t* trace_mu, uint32_t* trace_iters, void* scratch, hipStream_t st);
 
 // SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" verification over n rows of one chunk (slhdsa.hip).  which =
 // slhdsa_find(name): 2 set + flavour (set 0, 1, 2 = 128f, 192f, 256f; flavour 0 = "SPHINCS+-SHA2-*f-simple",

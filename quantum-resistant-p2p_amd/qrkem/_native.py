@@ -69,6 +69,8 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_sig_verify_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P]),
         "qrk_sig_keypair_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P]),
         "qrk_sig_sign_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P]),
+        "qrk_mldsa_keypair_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P]),
+        "qrk_mldsa_sign_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P]),
         "qrk_base64_encode_batch": (ct.c_int, [P, SZ, P, SZ, P, P]),
         "qrk_base64_decode_batch": (ct.c_int, [P, SZ, P, SZ, P, P, P]),
         "qrk_ctx_profile": (ct.c_int, [P, ct.c_int]),

@@ -13,8 +13,14 @@ verifies the messages it receives here, in batches (:meth:`verify_batch`).  That
 ``qrk_sig_sign_batch``, slhdsa_sign.hip: FIPS 205 Algorithms 18 and 19): ``generate_keypair`` and ``sign`` as
 the reference calls them, :meth:`SPHINCSSignature.generate_keypair_batch` and
 :meth:`SPHINCSSignature.sign_batch` over device tensors.  Signing is hedged (a fresh ``opt_rand`` per
-signature) unless ``deterministic=True``.  A node on the SPHINCS+ path then needs no liboqs; ML-DSA signing
-still does.  Like ``_native.py`` there is no CPU fallback.
+signature) unless ``deterministic=True``.  A node on the SPHINCS+ path then needs no liboqs.
+
+``MLDSASigner`` does the same for ML-DSA, the reference's default signature: a subclass of ``MLDSASignature``
+with ``generate_keypair`` / ``sign`` and their ``*_batch`` forms over ``qrk_mldsa_keypair_batch`` /
+``qrk_mldsa_sign_batch`` (mldsa_sign.hip: FIPS 204 Algorithms 6 and 2, hedged unless ``deterministic=True``).
+``MLDSASignature`` itself and the generic ``qrk_sig_keypair_batch`` / ``qrk_sig_sign_batch`` deliberately keep
+refusing ML-DSA signing, so code written against the verify-only class keeps its errors.  With ``MLDSASigner``
+a default node needs no liboqs for signatures either.  Like ``_native.py`` there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -191,6 +197,84 @@ class MLDSASignature(_BatchVerifier):
     def description(self) -> str:
         return ("ML-DSA is a lattice-based digital signature scheme. "
                 "It is one of the NIST post-quantum cryptography standards.")
+
+
+class MLDSASigner(MLDSASignature):
+    """ML-DSA with key generation and signing on the GPU as well (``qrk_mldsa_keypair_batch`` /
+    ``qrk_mldsa_sign_batch``, mldsa_sign.hip: FIPS 204 Algorithms 6 and 2 with the empty context string, what
+    liboqs's ``OQS_SIG_sign`` produces).  ``generate_keypair`` and ``sign`` are the reference's calls
+    (signatures.py:100-152); the ``*_batch`` methods work on device tensors.  Signing is hedged (32 fresh bytes of
+    ``rnd`` per signature) unless ``deterministic=True`` (rnd = 32 zero bytes, which reproduces a signature bit
+    for bit).  :class:`MLDSASignature` itself stays verification-only."""
+
+    def __init__(self, security_level: int = 3, device: int = 0, deterministic: bool = False):
+        super().__init__(security_level, device)
+        self.deterministic = bool(deterministic)
+
+    def generate_keypair(self) -> Tuple[bytes, bytes]:
+        """(public key, secret key) from 32 fresh bytes of the OS CSPRNG."""
+        pk, sk = self.generate_keypair_batch(1)
+        return pk[0].cpu().numpy().tobytes(), sk[0].cpu().numpy().tobytes()
+
+    def sign(self, private_key: bytes, message: bytes) -> bytes:
+        """The signature of `message`.  Unlike ``verify`` this raises on any error, as the reference's does."""
+        ctx = self._context()  # noqa: F841  (first: without a device this is the error to raise)
+        if len(private_key) != self.secret_key_size:
+            raise ValueError(f"{self.FAMILY} secret keys of {self.variant} have {self.secret_key_size} bytes, "
+                             f"got {len(private_key)}")
+        return self.sign_batch([bytes(private_key)], [bytes(message)])[0].cpu().numpy().tobytes()
+
+    def generate_keypair_batch(self, n: int, seeds=None):
+        """n key pairs: device tensors (pk [n, pk bytes], sk [n, sk bytes]).  ``seeds``: [n, 32] uint8, the xi of
+        FIPS 204 Algorithm 6 per row (a device tensor, numpy array or list of bytes); None draws them from
+        ``os.urandom``."""
+        ctx = self._context()
+        if seeds is None:
+            seeds = np.frombuffer(os.urandom(n * 32), np.uint8).reshape(n, 32)
+        if not _is_dev(seeds):
+            seeds = _dev(_as_host(seeds, 32), self.device)
+        _check_dev(seeds, 32, f"{self.FAMILY} key seeds", n)
+        pk = torch.empty((n, self.public_key_size), dtype=torch.uint8, device=seeds.device)
+        sk = torch.empty((n, self.secret_key_size), dtype=torch.uint8, device=seeds.device)
+        rc = LIB.qrk_mldsa_keypair_batch(ctx, self.variant.encode(), n, _ptr(seeds), _ptr(pk), _ptr(sk), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} key generation failed ({self.variant}): {last_error()}")
+        return pk, sk
+
+    def sign_batch(self, private_keys, messages, offsets=None, rnd=None, return_status: bool = False):
+        """sig[i] = Sign(private_keys[i], messages[i]): a uint8 device tensor [n, signature bytes].
+
+        ``private_keys`` [n, sk bytes] and ``messages`` / ``offsets`` as in :meth:`verify_status`.  ``rnd``
+        [n, 32]: the per-row randomiser; None draws it from ``os.urandom``, or uses 32 zero bytes (the
+        deterministic variant of FIPS 204) if the object was made with ``deterministic=True``.  A row the
+        library refuses (status -1: offsets that decrease, 2^31 bytes or more, a corrupt key, or a rejection
+        loop that reached its cap of 814 iterations) has an all-zero signature; that raises ``RuntimeError``
+        unless ``return_status=True``, which returns ``(signatures, status)`` with the int32 [n] device tensor
+        instead."""
+        ctx = self._context()
+        messages, offsets, n = self._ragged(messages, offsets)
+        if not _is_dev(private_keys):
+            private_keys = _dev(_as_host(private_keys, self.secret_key_size), self.device)
+        _check_dev(private_keys, self.secret_key_size, f"{self.FAMILY} secret keys", n)
+        if rnd is None and not self.deterministic:
+            rnd = np.frombuffer(os.urandom(n * 32), np.uint8).reshape(n, 32)
+        if rnd is not None:
+            if not _is_dev(rnd):
+                rnd = _dev(_as_host(rnd, 32), self.device)
+            _check_dev(rnd, 32, f"{self.FAMILY} rnd", n)
+        sig = torch.empty((n, self.signature_size), dtype=torch.uint8, device=messages.device)
+        status = torch.empty((n,), dtype=torch.int32, device=messages.device)
+        rc = LIB.qrk_mldsa_sign_batch(ctx, self.variant.encode(), n, _ptr(private_keys), _ptr(messages), _ptr(offsets),
+                                      _ptr(rnd), None, 0, _ptr(sig), _ptr(status), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {last_error()}")
+        if return_status:
+            return sig, status
+        bad = int((status != 0).sum())  # the one host wait of this path
+        if bad:
+            raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {bad} of {n} rows were refused "
+                               "(corrupt secret key, malformed message offsets, or the iteration cap)")
+        return sig
 
 
 class SPHINCSSignature(_BatchVerifier):
