@@ -348,6 +348,46 @@ int qrk_mldsa_sign_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t 
                          const uint64_t *msg_off, const uint8_t *rnd, const uint8_t *ctx_str, size_t ctx_len,
                          uint8_t *sig, int32_t *status, void *stream);
 
+/* ML-DSA key sets: many rows under few keys.  A node verifies what each peer sends against that peer's one key
+ * and signs everything with its own (messaging.py:600-620, 721, 864, 933, 1090, 1174, 1480, 1622); the calls above
+ * redo per row what depends on the key alone (ExpandA, tr, the NTTs of t1 or of s1, s2, t0).  A key set holds g
+ * keys expanded once, and the keyed calls take an index into it per row.
+ *
+ * Load: pk [g][pk bytes] or sk [g][sk bytes], device pointers; *out receives the handle.  The expansion is
+ * stream-ordered on `stream`: calls that use the set on another stream must be ordered behind it by the caller,
+ * and `pk` / `sk` may be released once that stream has passed the load.  Checked before any device work, in this
+ * order: null context, name (anything but the three ML-DSA names: -1 "unsupported signature algorithm"), g == 0,
+ * null pointers, g beyond what the context's scratch budget rule allows for one allocation.  A set holds
+ * 20544 / 36928 / 65600 (public) or 28804 / 48260 / 81028 (secret) bytes of device memory per key for
+ * ML-DSA-44 / 65 / 87.  A secret set holds K and the NTTs of s1, s2 and t0 of its keys: next to the caller's sk
+ * rows and the signatures it is the only place in device memory with secret-derived bytes.
+ * qrk_mldsa_keyset_free synchronises the device, zeroes the whole allocation and then frees it (NULL: no-op);
+ * free a set before the device is reset.  qrk_ctx_cleanse does not touch key sets.
+ * qrk_mldsa_keyset_info: out = { g, parameter set (0, 1, 2 = ML-DSA-44, 65, 87), 1 if secret, device bytes held }. */
+typedef struct qrk_mldsa_keyset qrk_mldsa_keyset;
+int qrk_mldsa_pubkeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *pk, qrk_mldsa_keyset **out,
+                           void *stream);
+int qrk_mldsa_seckeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *sk, qrk_mldsa_keyset **out,
+                           void *stream);
+int qrk_mldsa_keyset_info(const qrk_mldsa_keyset *ks, size_t out[4]);
+void qrk_mldsa_keyset_free(qrk_mldsa_keyset *ks);
+/* Verify / Sign under a key set: row i uses key key_index[i] (uint32 [n], a device pointer; NULL means "every
+ * row uses key 0" and is accepted only when g == 1); every other argument as in qrk_sig_verify_batch /
+ * qrk_mldsa_sign_batch, and so are the results: byte for byte what those calls return for the same keys.  An
+ * index >= g is checked on the device before anything is addressed with it and makes the row a refused one:
+ * status -1 (and an all-zero signature when signing).  A row that names a secret key with an s1 / s2 coefficient
+ * outside [-eta, eta] is refused in the same way.  Checked before any device work, in this order: null context;
+ * a null or foreign key set (loaded on another device than the context's, or a public set passed to the signing
+ * call / a secret set to the verifying one), with a message that says which; ctx_len > 255; then n == 0 returns
+ * 0; then null buffers.  The context's scratch grows by 1092 / 1092 / 1348 bytes per verified row and 68 bytes per
+ * signed row (public values only). */
+int qrk_mldsa_verify_keyed_batch(qrk_ctx *ctx, const qrk_mldsa_keyset *ks, size_t n, const uint32_t *key_index,
+                                 const uint8_t *msg, const uint64_t *msg_off, const uint8_t *sig,
+                                 const uint8_t *ctx_str, size_t ctx_len, int32_t *status, void *stream);
+int qrk_mldsa_sign_keyed_batch(qrk_ctx *ctx, const qrk_mldsa_keyset *ks, size_t n, const uint32_t *key_index,
+                               const uint8_t *msg, const uint64_t *msg_off, const uint8_t *rnd,
+                               const uint8_t *ctx_str, size_t ctx_len, uint8_t *sig, int32_t *status, void *stream);
+
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853
  * ciphertext and responder key; decoded at :829 with base64.b64decode).  Device pointers,

@@ -1497,6 +1497,179 @@ extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t 
   return mldsa_verify_rows(ctx, a, n, v, MldsaTrace{mu, ctilde, w1, flags}, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ ML-DSA key sets (mldsa_keyed.hip)
+// g keys expanded once into one device allocation of their own (not the context's scratch: a set outlives calls
+// and contexts).  A secret set holds K and the NTTs of s1, s2, t0: qrk_mldsa_keyset_free zeroes it before freeing.
+struct qrk_mldsa_keyset {
+  int device = 0;
+  int which = 0;
+  bool secret = false;
+  size_t g = 0;
+  void* mem = nullptr;
+  size_t bytes = 0;
+  MldsaKeys view;
+};
+
+static int keyset_load(qrk_ctx* ctx, const char* alg, bool secret, size_t g, const uint8_t* keys,
+                       qrk_mldsa_keyset** out, hipStream_t st) {
+  if (!ctx) return fail("null context");
+  const int which = mldsa_find(alg);
+  if (which < 0) return sig_unsupported(alg);
+  if (g == 0) return fail("a key set holds at least one key (g == 0)");
+  if (!keys || !out) return fail("null buffer");
+  const size_t per_key = mldsa_keyset_bytes(which, secret, 1);
+  if (g > verify_cap(per_key))
+    return fail(std::string(alg) + ": a key set of " + std::to_string(g) + " keys exceeds the scratch budget (at most " +
+                std::to_string(verify_cap(per_key)) + " keys of " + std::to_string(per_key) + " bytes)");
+  CallScope scope;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::TIMER)) return -1;
+  qrk_mldsa_keyset* ks = new qrk_mldsa_keyset;
+  ks->device = ctx->device, ks->which = which, ks->secret = secret, ks->g = g;
+  ks->bytes = mldsa_keyset_bytes(which, secret, g);
+  hipError_t e = hipMalloc(&ks->mem, ks->bytes);
+  if (e != hipSuccess) {
+    delete ks;
+    return hip_fail("hipMalloc(key set)", e);
+  }
+  ks->view = mldsa_keyset_view(which, secret, g, ks->mem);
+  e = mldsa_keyset_expand(which, secret, g, keys, ks->mem, st);
+  if (e != hipSuccess) {
+    qrk_mldsa_keyset_free(ks);
+    return hip_fail("mldsa_keyset_expand", e);
+  }
+  *out = ks;
+  return 0;
+}
+
+int qrk_mldsa_pubkeys_load(qrk_ctx* ctx, const char* alg, size_t g, const uint8_t* pk, qrk_mldsa_keyset** out,
+                           void* stream) {
+  return keyset_load(ctx, alg, false, g, pk, out, (hipStream_t)stream);
+}
+
+int qrk_mldsa_seckeys_load(qrk_ctx* ctx, const char* alg, size_t g, const uint8_t* sk, qrk_mldsa_keyset** out,
+                           void* stream) {
+  return keyset_load(ctx, alg, true, g, sk, out, (hipStream_t)stream);
+}
+
+int qrk_mldsa_keyset_info(const qrk_mldsa_keyset* ks, size_t out[4]) {
+  if (!ks || !out) return fail(ks ? "null buffer" : "null key set");
+  out[0] = ks->g, out[1] = (size_t)ks->which, out[2] = ks->secret ? 1 : 0, out[3] = ks->bytes;
+  return 0;
+}
+
+void qrk_mldsa_keyset_free(qrk_mldsa_keyset* ks) {
+  if (!ks) return;
+  if (ks->mem) {
+    DeviceGuard guard;
+    if (guard.set(ks->device) == 0) {
+      (void)hipDeviceSynchronize();  // no launch that reads the set is still running
+      (void)hipMemset(ks->mem, 0, ks->bytes);
+      (void)hipDeviceSynchronize();
+      (void)hipFree(ks->mem);
+    }
+  }
+  delete ks;
+}
+
+// The argument checks of the two keyed calls and their trace hooks, in the order qrkem.h documents.  `bufs`: no
+// required pointer is null.  -1: failed, 1: n == 0, 0: go.  ctx is not dereferenced before ks is known to be set.
+static int keyed_args(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, bool signing, const uint32_t* key_index, size_t ctx_len,
+                      size_t n, bool bufs) {
+  if (!ctx) return fail("null context");
+  if (!ks) return fail("null key set");
+  if (ks->device != ctx->device)
+    return fail("foreign key set: it was loaded on device " + std::to_string(ks->device) + ", the context is on device " +
+                std::to_string(ctx->device));
+  if (signing && !ks->secret)
+    return fail("foreign key set: a public key set cannot sign (load the secret keys with qrk_mldsa_seckeys_load)");
+  if (!signing && ks->secret)
+    return fail("foreign key set: a secret key set cannot verify (load the public keys with qrk_mldsa_pubkeys_load)");
+  if (ctx_len > 255) return fail("ML-DSA context strings are at most 255 bytes");
+  if (n == 0) return 1;
+  if (!bufs) return fail("null buffer");
+  if (!key_index && ks->g != 1)
+    return fail("null buffer: key_index may be NULL only for a key set of one key");
+  return 0;
+}
+
+// qrk_mldsa_verify_keyed_batch and its traced twin: one body
+static int mldsa_verify_keyed_call(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                   const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
+                                   const uint8_t* ctx_str, size_t ctx_len, int32_t* status, const MldsaTrace& trace,
+                                   hipStream_t st) {
+  const bool bufs = msg && msg_off && sig && status && (ctx_str || !ctx_len);
+  if (const int r = keyed_args(ctx, ks, false, key_index, ctx_len, n, bufs)) return r < 0 ? -1 : 0;
+  const SigSizes sz = mldsa_sizes(ks->which);
+  return run_rows(ctx, st, n, verify_cap(mldsa_keyed_scratch_bytes(ks->which, 1)), mldsa_keyed_scratch_bytes, ks->which,
+                  "mldsa_verify_keyed", [&](size_t off, size_t m) {
+                    return mldsa_verify_keyed(ks->which, ks->view, m, key_index ? key_index + off : nullptr, msg,
+                                              msg_off + off, sig + off * sz.sig, ctx_str, ctx_len, status + off,
+                                              mldsa_trace_at(ks->which, trace, off), ctx->scratch, st);
+                  });
+}
+
+int qrk_mldsa_verify_keyed_batch(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                 const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str,
+                                 size_t ctx_len, int32_t* status, void* stream) {
+  return mldsa_verify_keyed_call(ctx, ks, n, key_index, msg, msg_off, sig, ctx_str, ctx_len, status, MldsaTrace{},
+                                 (hipStream_t)stream);
+}
+
+// Tests only (not in qrkem.h): qrk_mldsa_verify_keyed_batch with the trace outputs of qrk_dbg_mldsa_verify_trace; the
+// flag word has one more bit, 16: the row's key index is outside the set (zeros in the other three outputs).
+extern "C" int qrk_dbg_mldsa_verify_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n,
+                                                const uint32_t* key_index, const uint8_t* msg, const uint64_t* msg_off,
+                                                const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                                                int32_t* status, uint8_t* mu, uint8_t* ctilde, uint8_t* w1,
+                                                uint32_t* flags, void* stream) {
+  if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
+  return mldsa_verify_keyed_call(ctx, ks, n, key_index, msg, msg_off, sig, ctx_str, ctx_len, status,
+                                 MldsaTrace{mu, ctilde, w1, flags}, (hipStream_t)stream);
+}
+
+// qrk_mldsa_sign_keyed_batch and its traced twin qrk_dbg_mldsa_sign_keyed_trace (iters != NULL): one body
+static int mldsa_sign_keyed_call(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                 const uint8_t* msg, const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str,
+                                 size_t ctx_len, uint8_t* sig, int32_t* status, uint32_t max_iters, bool traced,
+                                 uint8_t* mu, uint32_t* iters, hipStream_t st) {
+  const bool bufs = msg && msg_off && sig && status && (ctx_str || !ctx_len) && (!traced || (mu && iters));
+  if (const int r = keyed_args(ctx, ks, true, key_index, ctx_len, n, bufs)) return r < 0 ? -1 : 0;
+  const SigSizes sz = mldsa_sizes(ks->which);
+  return run_rows(ctx, st, n, verify_cap(mldsa_keyed_sign_scratch_bytes(ks->which, 1)), mldsa_keyed_sign_scratch_bytes,
+                  ks->which, "mldsa_sign_keyed", [&](size_t off, size_t m) {
+                    return mldsa_sign_keyed(ks->which, ks->view, m, key_index ? key_index + off : nullptr, msg,
+                                            msg_off + off, rnd ? rnd + off * 32 : nullptr, ctx_str, ctx_len,
+                                            sig + off * sz.sig, status + off, max_iters,
+                                            traced ? mu + off * 64 : nullptr, traced ? iters + off : nullptr,
+                                            ctx->scratch, st);
+                  });
+}
+
+int qrk_mldsa_sign_keyed_batch(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                               const uint8_t* msg, const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str,
+                               size_t ctx_len, uint8_t* sig, int32_t* status, void* stream) {
+  return mldsa_sign_keyed_call(ctx, ks, n, key_index, msg, msg_off, rnd, ctx_str, ctx_len, sig, status,
+                               MLDSA_SIGN_MAX_ITERS, false, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// Tests only (not in qrkem.h): qrk_mldsa_sign_keyed_batch with the loop's cap as an argument and the outputs of
+// qrk_dbg_mldsa_sign_trace: mu [n][64] (zeros for a refused row) and the iterations run, iters [n].
+extern "C" int qrk_dbg_mldsa_sign_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n,
+                                              const uint32_t* key_index, const uint8_t* msg, const uint64_t* msg_off,
+                                              const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig,
+                                              int32_t* status, uint32_t max_iters, uint8_t* mu, uint32_t* iters,
+                                              void* stream) {
+  return mldsa_sign_keyed_call(ctx, ks, n, key_index, msg, msg_off, rnd, ctx_str, ctx_len, sig, status, max_iters, true,
+                               mu, iters, (hipStream_t)stream);
+}
+
+// Tests and tools only (not in qrkem.h): which form of the keyed signing core later launches take (1: the NTT'd
+// secret vectors held in LDS, 2: read from the set; anything else: the default).  Returns the mode now set.
+extern "C" int qrk_dbg_mldsa_keyed_sign_mode(int mode) {
+  g_mldsa_keyed_sign_mode.store(mode == 1 || mode == 2 ? mode : MLDSA_KEYED_SIGN_DEFAULT, std::memory_order_relaxed);
+  return g_mldsa_keyed_sign_mode.load(std::memory_order_relaxed);
+}
+
 // Tests only (not in qrkem.h): qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name that also writes, per row,
 // the H_msg digest [n][m], the FORS public key [n][n], the root every hypertree layer reconstructed
 // [n][d][n] and a flag word (bit 0: the top root differs from PK.root; bit 1, internal: a row of 2^31

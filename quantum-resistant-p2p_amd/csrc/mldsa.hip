@@ -20,8 +20,7 @@
 // core kernel's workgroup at once).  Nothing here may be copied into a signing path.
 #include <cstring>
 
-#include "mldsa_common.cuh"
-#include "qrkem_internal.h"
+#include "mldsa_cores.cuh"
 
 namespace qrk {
 namespace mldsa {
@@ -54,27 +53,7 @@ __global__ __launch_bounds__(64) void k_mldsa_front(size_t n, const uint8_t* __r
       // mu: the 64 bytes of tr are the first 8 words of the next sponge's first block
 #pragma unroll
       for (int w = 8; w < 25; ++w) s.a[w] = {0u, 0u};
-      absorb_bytes<RW_SHAKE256, 8>(s, 2 + ctx_len + mlen, [&](uint32_t i) -> uint32_t {
-        if (i < 2) return i ? ctx_len : 0u;
-        i -= 2;
-        return i < ctx_len ? ctx[i] : m[i - ctx_len];
-      });
-#pragma unroll
-      for (int w = 0; w < 8; ++w) mu[row * 8 + w] = kword(s, w);
-      // c = SampleInBall(c~)
-      const uint8_t* ct = sig + row * P.sig;
-      bool started = false;
-      sample_in_ball(P.tau, (int8_t*)cs[lane], (uint8_t*)sb[lane], [&](uint8_t*) {
-        if (!started) {
-          kzero(s);
-          absorb_bytes<RW_SHAKE256, 0>(s, P.ctilde, [&](uint32_t i) -> uint32_t { return ct[i]; });
-          started = true;
-        } else {
-          keccak_f(s);
-        }
-#pragma unroll
-        for (int w = 0; w < 17; ++w) sb[lane][w] = kword(s, w);
-      });
+      front_mu_c<PS>(s, row, m, mlen, ctx, ctx_len, sig + row * P.sig, mu, (int8_t*)cs[lane], sb[lane]);
     }
     flags[row] = fl;
   }
@@ -95,52 +74,10 @@ __global__ __launch_bounds__(256) void k_mldsa_core(const uint8_t* __restrict__ 
                                                     const int8_t* __restrict__ cpoly, uint8_t* __restrict__ w1,
                                                     uint32_t* __restrict__ flags) {
   constexpr Params P = Set<PS>::P;
-  constexpr int K = P.k, L = P.l;
-  __shared__ int zc[(L + 1) * N];  // z_hat[0 .. l), c_hat
-  __shared__ int tp[N];            // (t1 2^d)_hat of row i, then w'_approx of row i
-  __shared__ uint32_t hb[K * 8];   // the hint, one bit per coefficient
-  __shared__ uint8_t wv[N];
-  __shared__ uint32_t s_flag;
-  const int tid = threadIdx.x;
   const size_t row = blockIdx.x;
   if (flags[row] & FLAG_LONG) return;  // the whole workgroup: k_mldsa_front wrote nothing else for it
-  const uint8_t* sg = sig + row * P.sig;
-  const uint8_t* pkr = pk + row * P.pk;
-  if (tid < K * 8) hb[tid] = 0;
-  if (tid == 0) s_flag = 0;
-  __syncthreads();
-  if (tid == 0 && !hint_unpack(sg + P.hint_off(), K, P.omega, hb)) s_flag = FLAG_HINT;
-  bool over = false;
-  for (int e = tid; e < L * N; e += 256) {
-    const int z = z_coeff(sg + P.ctilde + (e >> 8) * 32 * P.zbits, P.zbits, P.gamma1, e & 255);
-    over |= (z < 0 ? -z : z) >= P.gamma1 - P.beta;
-    zc[e] = z;
-  }
-  zc[L * N + tid] = cpoly[row * N + tid];
-  __syncthreads();
-  if (s_flag & FLAG_HINT) {  // early exit (public input): w1 is undefined without the hint
-    if (tid == 0) flags[row] = FLAG_HINT;
-    return;
-  }
-  if (over) atomicOr(&s_flag, FLAG_NORM);
-  ntt_fwd(zc, L + 1, tid, 256);  // |z| <= gamma1, |c| <= 1: outputs below 2^25.1 (2^19 + 8 HALFQ)
-  for (int i = 0; i < K; ++i) {
-    tp[tid] = t1_coeff_2d(pkr + 32 + 320 * i, tid);
-    ntt_fwd(tp, 1, tid, 256);  // input in [0, q): output below 5 q < 2^25.4
-    // l + 1 products below 2^50.5 (A_hat in [0, q)); the sum is at most 8 HALFQ < 2^25
-    int acc = -modmul(zc[L * N + tid], (double)tp[tid]);
-    const int32_t* a = A + (row * K * L + (size_t)i * L) * N + tid;
-    for (int j = 0; j < L; ++j) acc += modmul(a[j * N], (double)zc[j * N + tid]);
-    tp[tid] = acc;
-    ntt_inv(tp, 1, tid, 256);
-    const int h = (hb[i * 8 + (tid >> 5)] >> (tid & 31)) & 1;
-    wv[tid] = (uint8_t)use_hint<P.gamma2>(h, canon(tp[tid]));
-    __syncthreads();
-    constexpr int NB = 32 * P.w1bits;
-    if (tid < NB) w1[row * P.w1_bytes() + i * NB + tid] = w1_byte(wv, P.w1bits, tid);
-    __syncthreads();
-  }
-  if (tid == 0) flags[row] = s_flag;
+  verify_core_body<PS, false>(row, sig + row * P.sig, pk + row * P.pk + 32, nullptr, A + row * P.k * P.l * N, cpoly,
+                              w1, flags);
 }
 
 // The trace outputs (tests: qrk_dbg_mldsa_verify_trace) are all set or all NULL.
@@ -149,42 +86,7 @@ __global__ __launch_bounds__(64) void k_mldsa_final(size_t n, const uint8_t* __r
                                                     const uint64_t* __restrict__ mu, const uint8_t* __restrict__ w1,
                                                     const uint32_t* __restrict__ flags, int32_t* __restrict__ status,
                                                     MldsaTrace tr) {
-  constexpr Params P = Set<PS>::P;
-  constexpr int CW = P.ctilde / 8;
-  const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= n) return;
-  uint32_t fl = flags[row];
-  const bool hashed = !(fl & (FLAG_HINT | FLAG_LONG));
-  KState s;
-  kzero(s);
-  if (hashed) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) kxor(s, w, mu[row * 8 + w]);
-    const uint8_t* wr = w1 + row * P.w1_bytes();
-    absorb_bytes<RW_SHAKE256, 8>(s, P.w1_bytes(), [&](uint32_t i) -> uint32_t { return wr[i]; });
-    const uint8_t* ct = sig + row * P.sig;
-    bool same = true;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) {
-      uint64_t v = 0;
-#pragma unroll
-      for (int b = 0; b < 8; ++b) v |= (uint64_t)ct[8 * w + b] << (8 * b);
-      same &= v == kword(s, w);
-    }
-    if (!same) fl |= FLAG_HASH;
-  }
-  status[row] = fl ? -1 : 0;
-  if (tr.flags) {
-    tr.flags[row] = fl;
-    uint64_t* tm = (uint64_t*)tr.mu + row * 8;
-    uint64_t* tc = (uint64_t*)tr.ctilde + row * 8;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      tm[w] = hashed ? mu[row * 8 + w] : 0;
-      tc[w] = hashed && w < CW ? kword(s, w) : 0;
-    }
-    for (int b = 0; b < P.w1_bytes(); ++b) tr.w1[row * P.w1_bytes() + b] = hashed ? w1[row * P.w1_bytes() + b] : 0;
-  }
+  verify_final_body<PS>(n, sig, mu, w1, flags, status, tr);
 }
 
 // scratch of a chunk of C rows: A_hat | mu | w1 | c | flags (every part a multiple of 8 bytes per row

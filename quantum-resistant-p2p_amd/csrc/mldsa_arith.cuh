@@ -24,8 +24,9 @@ constexpr int D = 13;
 constexpr int N = 256;
 constexpr int ZETA = 1753;
 constexpr int HALFQ = (Q + 1) / 2;  // 4190209: the bound of every modmul result
-// flag word of a row (qrk_dbg_mldsa_verify_trace); FLAG_LONG is internal: the row has 2^31 bytes or more
-constexpr uint32_t FLAG_HINT = 1, FLAG_NORM = 2, FLAG_HASH = 4, FLAG_LONG = 8;
+// flag word of a row (qrk_dbg_mldsa_verify_trace); FLAG_LONG is internal: the row has 2^31 bytes or more;
+// FLAG_KEY (key-set calls, mldsa_keyed.hip): the row's key index is not below the number of keys in the set
+constexpr uint32_t FLAG_HINT = 1, FLAG_NORM = 2, FLAG_HASH = 4, FLAG_LONG = 8, FLAG_KEY = 16;
 
 struct Params {
   int k, l, tau, ctilde, zbits, gamma1, gamma2, omega, beta, w1bits;

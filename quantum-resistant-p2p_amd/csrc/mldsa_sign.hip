@@ -20,7 +20,8 @@
 //
 // Secret handling.  xi, rho', K, rho'', s1, s2, t0, y and everything computed from them live in registers and LDS
 // only; the only global stores of secret-derived bytes are the `sk` rows KeyGen writes and the accepted
-// signature.  Every LDS array is zeroed before its workgroup exits.  Inside an iteration of the signing loop no
+// signature.  (A secret key set, mldsa_keyed.hip, is the third place: K, NTT(s1), NTT(s2) and NTT(t0) of its
+// keys stay in its own device allocation until qrk_mldsa_keyset_free zeroes it.)  Every LDS array is zeroed before its workgroup exits.  Inside an iteration of the signing loop no
 // branch and no address depends on s1, s2, t0, y, K or rho'': the norm and weight checks OR / add over all
 // coefficients into one LDS word and the workgroup decides once, after the last of them.  What does depend on
 // secret data is what the standard itself has: the accept / reject decision per iteration (so the iteration
@@ -34,49 +35,10 @@
 // sig and status of every row are written exactly once, by the core kernel.
 #include <cstring>
 
-#include "mldsa_common.cuh"
-#include "qrkem_internal.h"
+#include "mldsa_cores.cuh"
 
 namespace qrk {
 namespace mldsa {
-
-constexpr int T0_BYTES = 32 * D;  // one polynomial of t0, 13 bits per coefficient
-__host__ __device__ constexpr int eta_of(const Params& P) { return P.beta / P.tau; }
-__host__ __device__ constexpr int eta_bits(const Params& P) { return eta_of(P) == 2 ? 3 : 4; }
-
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) {
-  uint64_t v = 0;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) v |= (uint64_t)p[b] << (8 * b);
-  return v;
-}
-__device__ __forceinline__ void st64(uint8_t* p, uint64_t v) {
-#pragma unroll
-  for (int b = 0; b < 8; ++b) p[b] = (uint8_t)(v >> (8 * b));
-}
-// Field i of 256 fields of `bits` (<= 20) bits packed little-endian at p.  Reads only the bytes that hold
-// the field (up to three), so the last field reads nothing past the polynomial.  The address depends on i alone.
-__device__ __forceinline__ uint32_t field(const uint8_t* p, int bits, int i) {
-  const int bit = i * bits, o = bit >> 3, sh = bit & 7;
-  uint32_t v = p[o];
-  if (sh + bits > 8) v |= (uint32_t)p[o + 1] << 8;
-  if (sh + bits > 16) v |= (uint32_t)p[o + 2] << 16;
-  return (v >> sh) & ((1u << bits) - 1);
-}
-// Byte b of the packing of 256 fields val(i) < 2^bits.  256 bits is a whole number of bytes, so the last
-// byte ends with field 255 and no index beyond it is formed.
-template <class Val>
-__device__ __forceinline__ uint8_t packed_byte(int bits, int b, Val val) {
-  const int bit = 8 * b;
-  int i = bit / bits, have = bits - (bit - i * bits);  // what field i still has from position `bit` on
-  uint32_t x = val(i) >> (bits - have);
-  while (have < 8) {
-    ++i;
-    x |= val(i) << have;
-    have += bits;
-  }
-  return (uint8_t)x;
-}
 
 // ================================================================= KeyGen
 // (rho, rho', K) = H(xi || k || l, 128): on return s holds the 136-byte output block, rho in words 0..3,
@@ -215,27 +177,10 @@ __global__ __launch_bounds__(64) void k_mldsa_sign_mu(size_t n, const uint8_t* _
   constexpr Params P = Set<PS>::P;
   const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (row >= n) return;
-  const uint64_t o0 = off[row], o1 = off[row + 1];
-  const bool bad = o1 < o0 || o1 - o0 >= (1ull << 31);
-  KState s;
-  kzero(s);
-  if (!bad) {
-    const uint32_t mlen = (uint32_t)(o1 - o0);
-    const uint8_t* tr = sk + row * P.sk + 64;  // tr = H(pk, 64): public
-    const uint8_t* m = msg + o0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) kxor(s, w, ld64(tr + 8 * w));
-    absorb_bytes<RW_SHAKE256, 8>(s, 2 + ctx_len + mlen, [&](uint32_t i) -> uint32_t {
-      if (i < 2) return i ? ctx_len : 0u;
-      i -= 2;
-      return i < ctx_len ? ctx[i] : m[i - ctx_len];
-    });
-  }
-#pragma unroll
-  for (int w = 0; w < 8; ++w) mu[row * 8 + w] = kword(s, w);  // zeros for a flagged row
-  flags[row] = bad ? FLAG_LONG : 0u;
+  sign_mu_body(row, sk + row * P.sk + 64, 0u, msg, off, ctx, ctx_len, mu, flags);  // tr = H(pk, 64): public
 }
 
+// The loop itself is sign_core_body (mldsa_cores.cuh), which the key-set call shares; here the key is the row's own.
 // TRACE (tests: qrk_dbg_mldsa_sign_trace) also stores mu and the iterations run; no other call launches that
 // instantiation.
 template <int PS, bool TRACE>
@@ -247,209 +192,11 @@ __global__ __launch_bounds__(256) void k_mldsa_sign_core(const uint8_t* __restri
                                                          uint8_t* __restrict__ sig, int32_t* __restrict__ status,
                                                          uint8_t* __restrict__ tr_mu, uint32_t* __restrict__ tr_iters) {
   constexpr Params P = Set<PS>::P;
-  constexpr int K = P.k, L = P.l, ETA = eta_of(P), EB = eta_bits(P), SB = 32 * EB;
-  constexpr int ZB = 32 * P.zbits;            // bytes of one packed polynomial of y or z
-  constexpr int YBLK = (ZB + 135) / 136;      // SHAKE256 blocks of one ExpandMask stream
-  constexpr int YW = YBLK * RW_SHAKE256;      // ... in words
-  constexpr int CW = P.ctilde / 8;
-  constexpr int W1B = 32 * P.w1bits;          // bytes of one polynomial of w1Encode
-  static_assert(2 * N * (int)sizeof(int) <= L * YW * 8, "the two-polynomial scratch fits the mask bytes");
-  // LDS: (3 k + 2 l + 1) KiB of coefficients, the mask bytes, 2 k 128 bytes of high bits, under 1 KiB of
-  // small buffers: 26064 / 35488 / 47696 bytes for ML-DSA-44 / 65 / 87.
-  __shared__ int s1h[L * N], s2h[K * N], t0h[K * N];  // NTT(s1), NTT(s2), NTT(t0)
-  __shared__ int y[L * N];                            // y_hat, then c s1, then z
-  __shared__ int w[K * N];                            // A_hat y_hat, then w
-  __shared__ int ch[N];                               // c_hat
-  __shared__ uint64_t yb[L * YW];  // the ExpandMask streams; once z is formed, two polynomials of scratch
-  __shared__ uint8_t wv[K * N];    // HighBits(w)
-  __shared__ int8_t cs[N];         // c
-  __shared__ uint64_t sb[RW_SHAKE256], rho2[8], mus[8], ctl[8];  // SampleInBall's block, rho'', mu, c~
-  __shared__ uint32_t hb[K * 8];   // the hint, one bit per coefficient
-  __shared__ uint8_t hbytes[P.omega + K];
-  __shared__ uint32_t s_bad, s_rej, s_hcnt;
-  const int tid = threadIdx.x;
   const size_t row = blockIdx.x;
   const uint8_t* skr = sk + row * P.sk;
-  uint8_t* sg = sig + row * P.sig;
-  if (tid == 0) s_bad = 0;
-  if (tid < 8) mus[tid] = mu[row * 8 + tid];
-  __syncthreads();
-  // skDecode; a field above 2 eta is outside [-eta, eta]: every field is looked at, the flag is set once
-  {
-    uint32_t over = 0;
-    for (int e = tid; e < L * N; e += 256) {
-      const uint32_t v = field(skr + 128 + (e >> 8) * SB, EB, e & 255);
-      over |= (uint32_t)(2 * ETA - (int)v) >> 31;
-      s1h[e] = ETA - (int)v;
-    }
-    for (int e = tid; e < K * N; e += 256) {
-      const uint32_t v = field(skr + 128 + (L + (e >> 8)) * SB, EB, e & 255);
-      over |= (uint32_t)(2 * ETA - (int)v) >> 31;
-      s2h[e] = ETA - (int)v;
-      t0h[e] = (1 << (D - 1)) - (int)field(skr + 128 + (L + K) * SB + (e >> 8) * T0_BYTES, D, e & 255);
-    }
-    atomicOr(&s_bad, over);
-  }
-  ntt_fwd(s1h, L, tid, 256);  // inputs within 2^12: outputs below 2^25
-  ntt_fwd(s2h, K, tid, 256);
-  ntt_fwd(t0h, K, tid, 256);
-  const bool refused = s_bad != 0 || flags[row] != 0;  // the same for the whole workgroup
-  uint32_t iters = 0;
-  bool done = false;
-  if (!refused) {
-    if (tid == 0) {  // rho'' = H(K || rnd || mu, 64): 128 bytes, one block
-      KState s;
-      kzero(s);
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        kxor(s, x, ld64(skr + 32 + 8 * x));
-        kxor(s, 4 + x, rnd ? ld64(rnd + row * 32 + 8 * x) : 0ull);
-      }
-#pragma unroll
-      for (int x = 0; x < 8; ++x) kxor(s, 8 + x, mus[x]);
-      s.a[16].lo ^= DS_SHAKE;
-      s.a[RW_SHAKE256 - 1].hi ^= 0x80000000u;
-      keccak_f(s);
-#pragma unroll
-      for (int x = 0; x < 8; ++x) rho2[x] = kword(s, x);
-    }
-    for (uint32_t it = 0; it < max_iters; ++it) {
-      if (tid == 0) s_rej = 0, s_hcnt = 0;
-      __syncthreads();
-      // ExpandMask (Algorithm 34): lane r squeezes H(rho'' || kappa + r as two bytes, 32 zbits bytes)
-      if (tid < L) {
-        KState s;
-        kzero(s);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) kxor(s, x, rho2[x]);
-        s.a[8].lo ^= (it * L + (uint32_t)tid) | (DS_SHAKE << 16);  // kappa + r <= 814 * 7 + 6 < 2^16
-        s.a[RW_SHAKE256 - 1].hi ^= 0x80000000u;
-        for (int blk = 0; blk < YBLK; ++blk) {
-          keccak_f(s);
-#pragma unroll
-          for (int x = 0; x < RW_SHAKE256; ++x) yb[tid * YW + blk * RW_SHAKE256 + x] = kword(s, x);
-        }
-      }
-      __syncthreads();
-      for (int e = tid; e < L * N; e += 256)
-        y[e] = P.gamma1 - (int)field((const uint8_t*)(yb + (e >> 8) * YW), P.zbits, e & 255);
-      ntt_fwd(y, L, tid, 256);  // |y| <= gamma1: outputs below 2^25.1
-      // w = INTT(A_hat y_hat): l products below 2^48.1 per coefficient, the sum at most 7 HALFQ
-      const int32_t* a = A + row * K * L * N + tid;
-      for (int i = 0; i < K; ++i) {
-        int acc = 0;
-        for (int j = 0; j < L; ++j) acc += modmul(a[(i * L + j) * N], (double)y[j * N + tid]);
-        w[i * N + tid] = acc;
-      }
-      ntt_inv(w, K, tid, 256);
-      for (int i = 0; i < K; ++i) {
-        int r1, r0;
-        decompose<P.gamma2>(canon(w[i * N + tid]), r1, r0);
-        wv[i * N + tid] = (uint8_t)r1;
-      }
-      __syncthreads();
-      // c~ = H(mu || w1Encode(w1), lambda / 4) and c = SampleInBall(c~): one sponge after the other on lane 0
-      if (tid == 0) {
-        KState s;
-        kzero(s);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) kxor(s, x, mus[x]);
-        absorb_bytes<RW_SHAKE256, 8>(s, P.w1_bytes(), [&](uint32_t i) -> uint32_t {
-          return w1_byte(wv + (i / W1B) * N, P.w1bits, i % W1B);
-        });
-#pragma unroll
-        for (int x = 0; x < 8; ++x) ctl[x] = x < CW ? kword(s, x) : 0ull;
-        kzero(s);
-#pragma unroll
-        for (int x = 0; x < CW; ++x) kxor(s, x, ctl[x]);
-        s.a[CW].lo ^= DS_SHAKE;
-        s.a[RW_SHAKE256 - 1].hi ^= 0x80000000u;
-        sample_in_ball(P.tau, cs, (uint8_t*)sb, [&](uint8_t*) {
-          keccak_f(s);
-#pragma unroll
-          for (int x = 0; x < RW_SHAKE256; ++x) sb[x] = kword(s, x);
-        });
-      }
-      __syncthreads();
-      ch[tid] = cs[tid];
-      ntt_fwd(ch, 1, tid, 256);  // outputs below 2^25
-      // z = y + c s1 (products below 2^50.1); c s1 is exact and within beta for a key that was not refused
-      for (int e = tid; e < L * N; e += 256) y[e] = modmul(s1h[e], (double)ch[e & 255]);
-      ntt_inv(y, L, tid, 256);
-      uint32_t rej = 0;
-      for (int e = tid; e < L * N; e += 256) {
-        const int z = P.gamma1 - (int)field((const uint8_t*)(yb + (e >> 8) * YW), P.zbits, e & 255) + y[e];
-        rej |= (uint32_t)(P.gamma1 - P.beta - 1 - (z < 0 ? -z : z)) >> 31;  // bit 0: ||z|| >= gamma1 - beta
-        y[e] = z;
-      }
-      __syncthreads();  // the mask bytes are dead: yb is scratch from here
-      // Row by row of the rest: r = w - c s2 and its low bits, c t0, the hint.  All of it runs in every
-      // iteration, whatever the checks before it found.
-      int* tmp = (int*)yb;
-      uint32_t hcnt = 0;
-      for (int i = 0; i < K; ++i) {
-        tmp[tid] = modmul(s2h[i * N + tid], (double)ch[tid]);
-        tmp[N + tid] = modmul(t0h[i * N + tid], (double)ch[tid]);
-        ntt_inv(tmp, 2, tid, 256);
-        const int r = w[i * N + tid] - tmp[tid], ct0 = tmp[N + tid];  // |r| <= 2 HALFQ; c t0 exact, <= tau 2^12
-        int r1, r0, v1, v0;
-        decompose<P.gamma2>(canon(r), r1, r0);
-        rej |= ((uint32_t)(P.gamma2 - P.beta - 1 - (r0 < 0 ? -r0 : r0)) >> 31) << 1;  // bit 1: LowBits
-        rej |= ((uint32_t)(P.gamma2 - 1 - (ct0 < 0 ? -ct0 : ct0)) >> 31) << 2;        // bit 2: ||c t0|| >= gamma2
-        decompose<P.gamma2>(canon(r + ct0), v1, v0);                                  // MakeHint(-c t0, r + c t0)
-        const unsigned long long bal = __ballot(v1 != r1);
-        if ((tid & 63) == 0) {
-          hb[i * 8 + (tid >> 6) * 2] = (uint32_t)bal;
-          hb[i * 8 + (tid >> 6) * 2 + 1] = (uint32_t)(bal >> 32);
-          hcnt += (uint32_t)__popcll(bal);
-        }
-      }
-      atomicOr(&s_rej, rej);
-      if ((tid & 63) == 0) atomicAdd(&s_hcnt, hcnt);
-      __syncthreads();
-      const bool reject = s_rej != 0 || s_hcnt > (uint32_t)P.omega;  // decided once, for the whole workgroup
-      iters = it + 1;
-      __syncthreads();  // every thread has read the two words before lane 0 clears them again
-      if (!reject) {
-        done = true;
-        break;
-      }
-    }
-  }
-  if (done) {  // sigEncode: everything stored from here on is the signature, public
-    if (tid < P.omega + K) hbytes[tid] = 0;
-    __syncthreads();
-    if (tid == 0) {
-      int index = 0;
-      for (int i = 0; i < K; ++i) {
-        for (int x = 0; x < 8; ++x)
-          for (uint32_t m = hb[i * 8 + x]; m; m &= m - 1) hbytes[index++] = (uint8_t)(32 * x + __builtin_ctz(m));
-        hbytes[P.omega + i] = (uint8_t)index;  // index <= omega: the weight check passed
-      }
-    }
-    __syncthreads();
-    for (int b = tid; b < P.ctilde; b += 256) sg[b] = ((const uint8_t*)ctl)[b];
-    for (int b = tid; b < L * ZB; b += 256) {
-      const int* z = y + (b / ZB) * N;
-      sg[P.ctilde + b] = packed_byte(P.zbits, b % ZB, [&](int i) -> uint32_t { return (uint32_t)(P.gamma1 - z[i]); });
-    }
-    if (tid < P.omega + K) sg[P.hint_off() + tid] = hbytes[tid];
-  } else {
-    for (int b = tid; b < P.sig; b += 256) sg[b] = 0;
-  }
-  if (tid == 0) status[row] = done ? 0 : -1;
-  if constexpr (TRACE) {
-    if (tid == 0) tr_iters[row] = iters;
-    if (tid < 64) tr_mu[row * 64 + tid] = ((const uint8_t*)mus)[tid];
-  }
-  __syncthreads();
-  for (int e = tid; e < L * N; e += 256) s1h[e] = 0, y[e] = 0;
-  for (int e = tid; e < K * N; e += 256) s2h[e] = 0, t0h[e] = 0, w[e] = 0, wv[e] = 0;
-  for (int e = tid; e < L * YW; e += 256) yb[e] = 0;
-  ch[tid] = 0, cs[tid] = 0;
-  if (tid < RW_SHAKE256) sb[tid] = 0;
-  if (tid < 8) rho2[tid] = 0, ctl[tid] = 0;
-  if (tid < K * 8) hb[tid] = 0;
+  sign_core_body<PS, TRACE, SIGN_ROW>(row, skr, SignKey{skr + 32, nullptr, nullptr, nullptr, 0u}, rnd,
+                                      A + row * P.k * P.l * N, mu + row * 8, flags[row], max_iters,
+                                      sig + row * P.sig, status, tr_mu, tr_iters);
 }
 
 // scratch of a chunk of C rows: A_hat | mu | flags

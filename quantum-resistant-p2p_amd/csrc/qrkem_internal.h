@@ -1,6 +1,6 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
 // launchers (mlkem.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
-// mldsa.hip, mldsa_sign.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
+// mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -259,6 +259,44 @@ hipError_t mldsa_keypair(int which, size_t n, const uint8_t* xi, uint8_t* pk, ui
 hipError_t mldsa_sign(int which, size_t n, const uint8_t* sk, const uint8_t* msg, const uint64_t* msg_off,
                       const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig, int32_t* status,
                       uint32_t max_iters, uint8_t* trace_mu, uint32_t* trace_iters, void* scratch, hipStream_t st);
+
+// ML-DSA key sets (mldsa_keyed.hip): g keys expanded once into one device allocation of mldsa_keyset_bytes, and
+// verification / signing of n rows that name their key by index.  MldsaKeys is the view of that allocation
+// (mldsa_keyset_view; device pointers): A_hat [g][k][l][256] for both kinds; a public set adds (t1 2^d)_hat
+// [g][k][256] reduced to [0, q) and tr [g][64]; a secret set adds NTT(s1) [g][l][256], NTT(s2) and NTT(t0)
+// [g][k][256], head [g][128] = rho | K | tr as in the secret key, and a refusal word per key (nonzero: an
+// s1 / s2 field outside [-eta, eta]).  Of these K and the three NTT'd vectors are secret.
+// key_index [n] (device; NULL: every row uses key 0) is checked against g on the device before any address is
+// formed from it: a row with an index >= g is refused (verification: status -1 and the flag word FLAG_KEY = 16;
+// signing: status -1 and an all-zero signature).  Everything else as mldsa_verify / mldsa_sign.  The scratch
+// holds public values only: mu, w1, c and a flag word per verified row, mu and a flag word per signed row.
+struct MldsaKeys {
+  uint32_t g = 0;
+  const int32_t* A = nullptr;
+  const int32_t* t1h = nullptr;
+  const int32_t *s1h = nullptr, *s2h = nullptr, *t0h = nullptr;
+  const uint8_t* head = nullptr;  // public: tr, 64 bytes per key; secret: rho | K | tr, 128 bytes per key
+  const uint32_t* bad = nullptr;
+};
+// Which form of the signing core a key-set launch takes: 1 copies the NTT'd secret vectors into LDS once per
+// workgroup, 2 reads them from the set in every iteration.  Same results; tools/mldsa_keyed_bench.py measures both
+// through qrk_dbg_mldsa_keyed_sign_mode, read (relaxed) at launch.  Measured equal within the run's spread at 2^14
+// rows, so the default is the form that is marginally ahead for a single signature ("ML-DSA key sets").
+constexpr int MLDSA_KEYED_SIGN_DEFAULT = 1;
+extern std::atomic<int> g_mldsa_keyed_sign_mode;
+size_t mldsa_keyset_bytes(int which, bool secret, size_t g);
+MldsaKeys mldsa_keyset_view(int which, bool secret, size_t g, void* mem);
+// keys: pk [g][pk] or sk [g][sk]; mem: mldsa_keyset_bytes, every byte of it is written
+hipError_t mldsa_keyset_expand(int which, bool secret, size_t g, const uint8_t* keys, void* mem, hipStream_t st);
+size_t mldsa_keyed_scratch_bytes(int which, size_t chunk);
+size_t mldsa_keyed_sign_scratch_bytes(int which, size_t chunk);
+hipError_t mldsa_verify_keyed(int which, const MldsaKeys& ks, size_t n, const uint32_t* key_index, const uint8_t* msg,
+                              const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                              int32_t* status, const MldsaTrace& trace, void* scratch, hipStream_t st);
+hipError_t mldsa_sign_keyed(int which, const MldsaKeys& ks, size_t n, const uint32_t* key_index, const uint8_t* msg,
+                            const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len,
+                            uint8_t* sig, int32_t* status, uint32_t max_iters, uint8_t* trace_mu,
+                            uint32_t* trace_iters, void* scratch, hipStream_t st);
 
 // SLH-DSA-SHA2 / SPHINCS+-SHA2-simple "f" verification over n rows of one chunk (slhdsa.hip).  which =
 // slhdsa_find(name): 2 set + flavour (set 0, 1, 2 = 128f, 192f, 256f; flavour 0 = "SPHINCS+-SHA2-*f-simple",

@@ -20,9 +20,9 @@ from .key_exchange import (  # noqa: F401
 # The symmetric layer (crypto/symmetric.py's surface over aead.hip) is re-exported on first use:
 # its module needs torch for device buffers, which `import qrkem` alone does not load.
 _SYMMETRIC = ("SymmetricAlgorithm", "AES256GCM", "ChaCha20Poly1305")
-# ... and so is the signature layer (crypto/signatures.py's surface over mldsa.hip, mldsa_sign.hip, slhdsa.hip
-# and slhdsa_sign.hip)
-_SIGNATURES = ("SignatureAlgorithm", "MLDSASignature", "MLDSASigner", "SPHINCSSignature")
+# ... and so is the signature layer (crypto/signatures.py's surface over mldsa.hip, mldsa_sign.hip,
+# mldsa_keyed.hip, slhdsa.hip and slhdsa_sign.hip)
+_SIGNATURES = ("SignatureAlgorithm", "MLDSASignature", "MLDSASigner", "MLDSAKeySet", "SPHINCSSignature")
 
 
 def __getattr__(name: str):

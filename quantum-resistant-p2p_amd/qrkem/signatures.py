@@ -21,6 +21,11 @@ with ``generate_keypair`` / ``sign`` and their ``*_batch`` forms over ``qrk_mlds
 ``MLDSASignature`` itself and the generic ``qrk_sig_keypair_batch`` / ``qrk_sig_sign_batch`` deliberately keep
 refusing ML-DSA signing, so code written against the verify-only class keeps its errors.  With ``MLDSASigner``
 a default node needs no liboqs for signatures either.  Like ``_native.py`` there is no CPU fallback.
+
+A node signs with one identity key and verifies each peer's messages against that peer's one key, so both ML-DSA
+classes also work on key sets (``MLDSAKeySet``, mldsa_keyed.hip): ``load_public_keys`` / ``load_secret_keys`` expand
+g keys once, and ``verify_keyed`` / ``sign_keyed`` take a key index per row and return what ``verify_batch`` /
+``sign_batch`` return for the same keys.
 """
 from __future__ import annotations
 
@@ -170,9 +175,63 @@ class _BatchVerifier(SignatureAlgorithm):
         return status
 
 
+class MLDSAKeySet:
+    """g ML-DSA keys expanded once on the device (``qrk_mldsa_pubkeys_load`` / ``qrk_mldsa_seckeys_load``,
+    mldsa_keyed.hip): what :meth:`MLDSASignature.verify_keyed` and :meth:`MLDSASigner.sign_keyed` index into.
+    Made by :meth:`MLDSASignature.load_public_keys` / :meth:`MLDSASigner.load_secret_keys`; owns the handle and
+    is a context manager.  A secret set holds secret-derived bytes in device memory until :meth:`close`, which
+    zeroes them (the library synchronises the device first)."""
+
+    def __init__(self, handle, variant: str, g: int, secret: bool, device: int = 0):
+        self._handle = handle
+        self.variant = variant
+        self.g = int(g)
+        self.secret = bool(secret)
+        self.device = device
+
+    @property
+    def closed(self) -> bool:
+        return not self._handle
+
+    @property
+    def device_bytes(self) -> int:
+        """Bytes of device memory the set holds (``qrk_mldsa_keyset_info``); 0 once closed."""
+        if self.closed:
+            return 0
+        out = (ct.c_size_t * 4)()
+        if LIB.qrk_mldsa_keyset_info(self._handle, out) != 0:
+            raise RuntimeError(last_error())
+        return int(out[3])
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            LIB.qrk_mldsa_keyset_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self) -> str:
+        kind = "secret" if self.secret else "public"
+        return f"<MLDSAKeySet {self.variant} {kind} g={self.g}{' closed' if self.closed else ''}>"
+
+
 class MLDSASignature(_BatchVerifier):
     """ML-DSA (FIPS 204) verification on one device.  The context is created on first use, so
-    constructing the object (as the reference does at start-up, messaging.py:128) needs no GPU."""
+    constructing the object (as the reference does at start-up, messaging.py:128) needs no GPU.
+
+    A node that hears from a handful of peers verifies many signatures under few keys:
+    :meth:`load_public_keys` expands the keys once and :meth:`verify_keyed` takes a key index per row."""
 
     VARIANTS = {2: "ML-DSA-44", 3: "ML-DSA-65", 5: "ML-DSA-87"}
     FAMILY = "ML-DSA"
@@ -184,6 +243,79 @@ class MLDSASignature(_BatchVerifier):
         self.security_level = security_level
         self.variant = self.VARIANTS[security_level]
         self._setup(device)
+
+    # ------------------------------------------------------------------ key sets
+    def _load_keys(self, keys, width: int, secret: bool) -> MLDSAKeySet:
+        ctx = self._context()  # first: without a device this is the error to raise
+        what = "secret" if secret else "public"
+        if not _is_dev(keys):
+            keys = _dev(_as_host(keys, width), self.device)
+        _check_dev(keys, width, f"{self.FAMILY} {what} keys")
+        g = keys.shape[0]
+        if g == 0:
+            raise ValueError(f"a key set holds at least one {what} key")
+        h = ct.c_void_p()
+        load = LIB.qrk_mldsa_seckeys_load if secret else LIB.qrk_mldsa_pubkeys_load
+        if load(ctx, self.variant.encode(), g, _ptr(keys), ct.byref(h), self._stream()) != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} key set load failed ({self.variant}): {last_error()}")
+        torch.cuda.current_stream(self.device).synchronize()  # the set is ready on every stream; `keys` may go
+        return MLDSAKeySet(h, self.variant, g, secret, self.device)
+
+    def _keyed_args(self, keyset, secret: bool, messages, offsets, key_index):
+        """The checks that need no device first (ValueError), then the context, then the device tensors."""
+        if not isinstance(keyset, MLDSAKeySet):
+            raise ValueError("keyset must be an MLDSAKeySet")
+        if keyset.variant != self.variant:
+            raise ValueError(f"the key set holds {keyset.variant} keys, this object is {self.variant}")
+        if keyset.secret and not secret:
+            raise ValueError("a secret key set cannot verify: load the public keys with load_public_keys")
+        if secret and not keyset.secret:
+            raise ValueError("a public key set cannot sign: load the secret keys with load_secret_keys")
+        if keyset.device != self.device:
+            raise ValueError(f"the key set is on device {keyset.device}, this object on device {self.device}")
+        if key_index is None and keyset.g != 1:
+            raise ValueError(f"key_index may be None only for a key set of one key, this one has {keyset.g}")
+        ctx = self._context()
+        if keyset.closed:
+            raise ValueError("the key set is closed")
+        messages, offsets, n = self._ragged(messages, offsets)
+        if key_index is not None:
+            if not _is_dev(key_index):
+                idx = np.asarray(key_index)
+                if idx.ndim != 1 or idx.dtype.kind not in "iu" or (idx.size and (idx.min() < 0 or idx.max() >= 2 ** 32)):
+                    raise ValueError("key_index must be a 1-D sequence of n indices in [0, 2^32)")
+                key_index = _dev(idx.astype(np.uint32).view(np.int32), self.device)
+            if key_index.dtype == torch.int64:
+                key_index = key_index.to(torch.int32)  # an index of 2^31 or more is outside every set either way
+            if not (key_index.dim() == 1 and key_index.numel() == n and key_index.is_contiguous() and
+                    key_index.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("key_index must be a contiguous 1-D 32-bit device tensor of n entries")
+        return ctx, messages, offsets, n, key_index
+
+    def load_public_keys(self, public_keys) -> MLDSAKeySet:
+        """A key set of the g public keys [g, pk bytes] (a device tensor, numpy array or list of bytes):
+        ExpandA, tr and the NTT of t1 run once per key here and never again per signature."""
+        return self._load_keys(public_keys, self.public_key_size, False)
+
+    def verify_keyed(self, keyset, messages, signatures, key_index=None, offsets=None):
+        """valid[i] = Verify(key key_index[i] of `keyset`, messages[i], signatures[i]): a numpy bool array [n],
+        the same answers as :meth:`verify_batch` with that key in row i.  ``key_index``: a sequence, numpy
+        array or device tensor of n indices; None (every row under key 0) only for a set of one key.  A row
+        whose index is not below ``keyset.g`` is invalid.  The other arguments as in :meth:`verify_batch`."""
+        return self.verify_keyed_status(keyset, messages, signatures, key_index, offsets).cpu().numpy() == 0
+
+    def verify_keyed_status(self, keyset, messages, signatures, key_index=None, offsets=None):
+        """As :meth:`verify_keyed`, returning the int32 [n] device tensor of the C ABI: 0 valid, -1 not."""
+        ctx, messages, offsets, n, key_index = self._keyed_args(keyset, False, messages, offsets, key_index)
+        if not _is_dev(signatures):
+            signatures = _dev(_as_host(signatures, self.signature_size), self.device)
+        _check_dev(signatures, self.signature_size, f"{self.FAMILY} signatures", n)
+        status = torch.empty((n,), dtype=torch.int32, device=messages.device)
+        rc = LIB.qrk_mldsa_verify_keyed_batch(ctx, keyset._handle, n, _ptr(key_index), _ptr(messages), _ptr(offsets),
+                                              _ptr(signatures), None, 0, _ptr(status), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} keyed verify failed ({self.variant}): {last_error()}")
+        return status
 
     @property
     def name(self) -> str:
@@ -274,6 +406,38 @@ class MLDSASigner(MLDSASignature):
         if bad:
             raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {bad} of {n} rows were refused "
                                "(corrupt secret key, malformed message offsets, or the iteration cap)")
+        return sig
+
+    def load_secret_keys(self, private_keys) -> MLDSAKeySet:
+        """A key set of the g secret keys [g, sk bytes]: ExpandA, skDecode and the NTTs of s1, s2 and t0 run once
+        per key.  The set keeps K and those NTTs in device memory until it is closed, which zeroes them."""
+        return self._load_keys(private_keys, self.secret_key_size, True)
+
+    def sign_keyed(self, keyset, messages, key_index=None, offsets=None, rnd=None, return_status: bool = False):
+        """sig[i] = Sign(key key_index[i] of `keyset`, messages[i]): a uint8 device tensor [n, signature bytes],
+        byte for byte what :meth:`sign_batch` gives with that key in row i.  ``key_index`` as in
+        :meth:`verify_keyed`; ``rnd`` and ``return_status`` as in :meth:`sign_batch`.  A row is refused (status
+        -1, an all-zero signature) for the reasons listed there, and when its index is not below ``keyset.g``."""
+        ctx, messages, offsets, n, key_index = self._keyed_args(keyset, True, messages, offsets, key_index)
+        if rnd is None and not self.deterministic:
+            rnd = np.frombuffer(os.urandom(n * 32), np.uint8).reshape(n, 32)
+        if rnd is not None:
+            if not _is_dev(rnd):
+                rnd = _dev(_as_host(rnd, 32), self.device)
+            _check_dev(rnd, 32, f"{self.FAMILY} rnd", n)
+        sig = torch.empty((n, self.signature_size), dtype=torch.uint8, device=messages.device)
+        status = torch.empty((n,), dtype=torch.int32, device=messages.device)
+        rc = LIB.qrk_mldsa_sign_keyed_batch(ctx, keyset._handle, n, _ptr(key_index), _ptr(messages), _ptr(offsets),
+                                            _ptr(rnd), None, 0, _ptr(sig), _ptr(status), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"qrkem {self.FAMILY} keyed sign failed ({self.variant}): {last_error()}")
+        if return_status:
+            return sig, status
+        bad = int((status != 0).sum())  # the one host wait of this path
+        if bad:
+            raise RuntimeError(f"qrkem {self.FAMILY} sign failed ({self.variant}): {bad} of {n} rows were refused "
+                               "(corrupt secret key, key index outside the set, malformed message offsets, or the "
+                               "iteration cap)")
         return sig
 
 
