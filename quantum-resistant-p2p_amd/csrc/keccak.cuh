@@ -3,13 +3,24 @@
 // The 25 64-bit lanes are held as 50 VGPRs (lo/hi 32-bit halves).  Per round:
 //   theta   : 20 v_bitop3 (column parity, XOR3) + 10 v_alignbit (rot-1)
 //             + 50 v_bitop3 (a ^ C[x-1] ^ rot(C[x+1]) fused as one XOR3 per half)
-//   rho/pi  : 48 v_alignbit/v_perm (funnel-shift rotates; pi is register renaming)
+//   rho/pi  : 44 v_alignbit + 4 v_perm (funnel-shift rotates; the compiler picks v_perm for offsets
+//             8 and 56; pi is register renaming)
 //   chi     : 50 v_bitop3 (a ^ (~b & c), selected by the compiler)
 //   iota    : 2 v_xor
-// = 180 VALU instructions per round, 4320 per permutation, no moves; 58 of them (the rotations)
-// issue at half rate on gfx950, and so do the 64-bit shifts that could replace them
-// (tools/rot64_probe.hip).  Two rounds per loop iteration (45.3 against 44.2 Top/s at one,
-// profiles/r2/rot64_unroll_probe.json).
+// = 180 VALU instructions per round, 4320 per permutation, no moves.  Two rounds per loop
+// iteration (45.3 against 44.2 Top/s at one, profiles/r2/rot64_unroll_probe.json).
+//
+// keccak_f_carry is the same permutation with theta's rot-1 as a carry chain (rol1x5 below: 15
+// v_add_co/v_addc_co in place of the 10 v_alignbit, 185 instructions per round, 4440 per
+// permutation).  Measured alone on gfx950, v_alignbit, v_perm, v_alignbyte, the 64-bit shifts and the
+// carry adds (SGPR pair or VCC) all issue at half the rate of v_xor (35-38 against 65 G per
+// lane-second), so by issue slots the carry form should lose; with many waves per SIMD it wins, 46.8
+// against 45.1 Top/s in the register-resident loop (tools/rot64_probe.hip,
+// profiles/keccak_rot/probe.json), and with one or two waves per SIMD it loses: its three stages
+// are a longer dependent chain than two funnel shifts, and the kernels that run a lane per
+// handshake at 2^16, the HQC hashes and FrodoKEM's streams measured 3-13 % slower with it
+// (profiles/keccak_rot/abx_other_all_sites.jsonl).  So the carry form is opt-in per call site, and
+// only SampleNTT's main pass (mlkem.hip, a lane per matrix entry: K^2 times the waves) takes it.
 // XOR3 is emitted through inline asm because hipcc (ROCm 7.2) splits
 // __builtin_amdgcn_bitop3_b32(...,0x96) back into two v_xor_b32.
 //
@@ -48,6 +59,39 @@ __device__ __forceinline__ u2 rol(u2 x) {
   }
 }
 
+// Theta's five rot-1 at once.  rol<1>(x) is x + x with the high half's carry added into the low
+// half and the low half's into the high: v_add_co_u32 lo, v_addc_co_u32 hi, v_addc_co_u32 lo + 0,
+// the carries in SGPR pairs so that VCC stays the compiler's.  On gfx950 a VALU that reads an SGPR
+// written by a VALU needs two wait states after the write, and nothing inside an asm string is
+// padded, so the five columns go stage by stage: four instructions separate every carry's write
+// from its read.  Keep every stage at three columns or more, in this order, or pad it: with fewer
+// instructions between a stage and the next the carries are read too early, silently.
+// (Left to the compiler -- __builtin_addc, or one asm statement per add -- each
+// dependent pair gets an s_nop and the loop is slower than with v_alignbit, profiles/keccak_rot.)
+__device__ __forceinline__ void rol1x5(const u2 (&C)[5], u2 (&R)[5]) {
+  uint64_t c0, c1, c2, c3, c4;
+  asm("v_add_co_u32 %0, %10, %15, %15\n\t"
+      "v_add_co_u32 %1, %11, %16, %16\n\t"
+      "v_add_co_u32 %2, %12, %17, %17\n\t"
+      "v_add_co_u32 %3, %13, %18, %18\n\t"
+      "v_add_co_u32 %4, %14, %19, %19\n\t"
+      "v_addc_co_u32 %5, %10, %20, %20, %10\n\t"
+      "v_addc_co_u32 %6, %11, %21, %21, %11\n\t"
+      "v_addc_co_u32 %7, %12, %22, %22, %12\n\t"
+      "v_addc_co_u32 %8, %13, %23, %23, %13\n\t"
+      "v_addc_co_u32 %9, %14, %24, %24, %14\n\t"
+      "v_addc_co_u32 %0, %10, %0, 0, %10\n\t"
+      "v_addc_co_u32 %1, %11, %1, 0, %11\n\t"
+      "v_addc_co_u32 %2, %12, %2, 0, %12\n\t"
+      "v_addc_co_u32 %3, %13, %3, 0, %13\n\t"
+      "v_addc_co_u32 %4, %14, %4, 0, %14"
+      : "=&v"(R[0].lo), "=&v"(R[1].lo), "=&v"(R[2].lo), "=&v"(R[3].lo), "=&v"(R[4].lo), "=&v"(R[0].hi),
+        "=&v"(R[1].hi), "=&v"(R[2].hi), "=&v"(R[3].hi), "=&v"(R[4].hi), "=&s"(c0), "=&s"(c1), "=&s"(c2),
+        "=&s"(c3), "=&s"(c4)
+      : "v"(C[0].lo), "v"(C[1].lo), "v"(C[2].lo), "v"(C[3].lo), "v"(C[4].lo), "v"(C[0].hi), "v"(C[1].hi),
+        "v"(C[2].hi), "v"(C[3].hi), "v"(C[4].hi));
+}
+
 __constant__ static const uint32_t KRC_LO[24] = {
     0x00000001u, 0x00008082u, 0x0000808au, 0x80008000u, 0x0000808bu, 0x80000001u,
     0x80008081u, 0x00008009u, 0x0000008au, 0x00000088u, 0x80008009u, 0x8000000au,
@@ -70,8 +114,8 @@ __device__ __forceinline__ void kzero(KState& s) {
   for (int i = 0; i < 25; ++i) s.a[i] = {0u, 0u};
 }
 
-// U rounds per loop iteration (24 = fully unrolled)
-template <int U = 2>
+// U rounds per loop iteration (24 = fully unrolled); CARRY: theta's rot-1 through rol1x5
+template <int U = 2, bool CARRY = false>
 __device__ __forceinline__ void keccak_fu(KState& s) {
 #pragma unroll U
   for (int r = 0; r < 24; ++r) {
@@ -81,8 +125,12 @@ __device__ __forceinline__ void keccak_fu(KState& s) {
       C[x].lo = xor3(xor3(s.a[x].lo, s.a[x + 5].lo, s.a[x + 10].lo), s.a[x + 15].lo, s.a[x + 20].lo);
       C[x].hi = xor3(xor3(s.a[x].hi, s.a[x + 5].hi, s.a[x + 10].hi), s.a[x + 15].hi, s.a[x + 20].hi);
     }
+    if constexpr (CARRY) {
+      rol1x5(C, R);
+    } else {
 #pragma unroll
-    for (int x = 0; x < 5; ++x) R[x] = rol<1>(C[x]);
+      for (int x = 0; x < 5; ++x) R[x] = rol<1>(C[x]);
+    }
 #pragma unroll
     for (int i = 0; i < 25; ++i) {
       const int x = i % 5;
@@ -128,6 +176,8 @@ __device__ __forceinline__ void keccak_fu(KState& s) {
   }
 }
 __device__ __forceinline__ void keccak_f(KState& s) { keccak_fu<2>(s); }
+// for kernels that keep several waves per SIMD busy with permutations (see the header)
+__device__ __forceinline__ void keccak_f_carry(KState& s) { keccak_fu<2, true>(s); }
 
 __device__ __forceinline__ void kxor(KState& s, int i, uint64_t w) {
   // i must be a compile-time constant after inlining

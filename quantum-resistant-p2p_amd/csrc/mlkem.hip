@@ -190,7 +190,10 @@ __device__ __forceinline__ void xof_blocks(KState& s, int& cnt, XUnit* __restric
   XofPend pd;
 #pragma unroll 1
   for (int b = 0; b < NB && (!ALL || cnt < 256); ++b) {
-    keccak_f(s);
+    // the main pass is throughput-bound (a lane per matrix entry), where the carry form of theta's
+    // rot-1 is the faster one; the fix-up is a wave or so per SIMD and keeps the funnel shifts
+    if constexpr (ALL) keccak_f(s);
+    else keccak_f_carry(s);
     compact_block<TW>(s, ring_all, rb, cnt, dst, pd);
   }
   xof_pend_store<TW>(pd, dst);

@@ -11,7 +11,10 @@ Every instruction between the end of the Keccak loop and the block loop's back-e
 by role; each triplet's two branches (the pending chunk's flush, the completed chunk's ring reads)
 run for the whole wave whenever any of its 64 lanes needs them, so they are counted once per
 triplet like the straight-line part.  Output: one JSON object (per block, per triplet, per
-candidate), the Keccak loop's counts alongside."""
+candidate), the Keccak loop's counts alongside.  The permutation issues 370 VALU per two-round
+iteration (4440 per permutation) against the algorithmic 4320: theta's five rot-1 are three carry
+adds each where the count has two operations (keccak_f_carry in keccak.cuh, SampleNTT's main pass
+only; keccak_f, everywhere else, is 360 = exactly 4320)."""
 import json
 import re
 import sys
