@@ -386,24 +386,42 @@ def test_sign_matches_the_per_row_call_and_the_spec(lib, ctx, keyed, signing_row
         assert "key_index" in qrkem.last_error()
 
 
+@pytest.fixture(scope="module")
+def golden_records():
+    return sgold.load()
+
+
 @gpu
 @pytest.mark.parametrize("name", SETS)
-def test_sign_replays_the_golden_records(lib, ctx, name):
-    """4: the records test_gpu_mldsa_sign.py replays from tests/golden/mldsa_sign.json (crafted keys among them)
-    reproduce through the keyed call: one set of the distinct secret keys, one index per record."""
-    rows = sgold.load()[name]["rows"]
-    sks = sorted({r["sk"] for r in rows})  # one key for a set without crafted records
-    with KeySet(lib, ctx, name, sks, True) as ks:
-        for ctx_len in (0, 255):
-            part = [r for r in rows if r["ctx_len"] == ctx_len]
-            sigs, status, mu, iters = sign_keyed(lib, ctx, ks, name, [r["msg"] for r in part],
-                                                 [sks.index(r["sk"]) for r in part], context=sgold.CTX255[:ctx_len],
-                                                 max_iters=814)
-            assert status == [0] * len(part)
-            for r, s, m, it in zip(part, sigs, mu, iters):
-                assert it == r["iters"], (r["kind"], r["counter"])
-                assert m == per_row_sign.mu_of(r["sk"], r["msg"], sgold.CTX255[:ctx_len])
-                assert hashlib.sha3_256(s).hexdigest() == r["sig_sha3"], (r["kind"], r["counter"])
+@pytest.mark.parametrize("mode", [1, 2])
+def test_sign_replays_the_golden_records(lib, ctx, golden_records, mode, name):
+    """4: the records test_gpu_mldsa_sign.py replays from tests/golden/mldsa_sign.json (crafted keys and the
+    threshold pairs among them) reproduce through the keyed call: one set of the distinct secret keys, one index
+    per record.  Under both builds of the signing core (1: the NTT'd secret vectors held in LDS, 2: read from the
+    set), each with status, mu, iteration counts and signatures equal to the per-row call's."""
+    rows = golden_records[name]["rows"]
+    sks = sorted({r["sk"] for r in rows})
+    lib.qrk_dbg_mldsa_keyed_sign_mode.restype = ct.c_int
+    lib.qrk_dbg_mldsa_keyed_sign_mode.argtypes = [ct.c_int]
+    try:
+        assert lib.qrk_dbg_mldsa_keyed_sign_mode(mode) == mode
+        with KeySet(lib, ctx, name, sks, True) as ks:
+            for ctx_len in (0, 255):
+                part = [r for r in rows if r["ctx_len"] == ctx_len]
+                msgs, context = [r["msg"] for r in part], sgold.CTX255[:ctx_len]
+                got = sign_keyed(lib, ctx, ks, name, msgs, [sks.index(r["sk"]) for r in part], context=context,
+                                 max_iters=814)
+                assert got == per_row_sign.sign(lib, ctx, name, [r["sk"] for r in part], msgs, context=context,
+                                                max_iters=814)
+                sigs, status, mu, iters = got
+                assert status == [0] * len(part)
+                for r, s, m, it in zip(part, sigs, mu, iters):
+                    assert it == r["iters"], (r["kind"], r["counter"])
+                    assert m == per_row_sign.mu_of(r["sk"], r["msg"], context)
+                    assert hashlib.sha3_256(s).hexdigest() == r["sig_sha3"], (r["kind"], r["counter"])
+    finally:
+        default = lib.qrk_dbg_mldsa_keyed_sign_mode(0)
+    assert default in (1, 2)
 
 
 @gpu

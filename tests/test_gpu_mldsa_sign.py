@@ -190,6 +190,32 @@ def test_batch_in_chunks(lib, sets, keys, name, n):
     assert mu == [mu_of(k, m) for k, m in zip(sks, msgs)]
 
 
+# ------------------------------------------------------------------ the four rejection thresholds
+@pytest.mark.parametrize("name", NAMES)
+def test_threshold_pairs(lib, ctx, sets, name):
+    """The fixture's threshold pairs in one batch: a row whose first iteration has ||z||, ||LowBits(w - c s2)||,
+    ||c t0|| or the hint count exactly on the rejecting value is rejected there, its twin one unit inside signs in
+    that iteration, and both give the spec's bytes (test_mldsa_sign_golden.py recomputes the exact values).  The
+    edge_h twin has omega hints: sigEncode writes the last byte of the index area."""
+    p = spec.PARAMS[name]
+    pairs = gold.stored_pairs(sets[name]["rows"])
+    assert [at["kind"] for at, _ in pairs] == ["edge_z"] * 2 + ["edge_r"] * 2 + \
+        ["edge_t"] * (2 if name == "ML-DSA-44" else 0) + ["edge_h"]
+    rows = [r for pair in pairs for r in pair]
+    sigs, status, mu, iters = sign(lib, ctx, name, [r["sk"] for r in rows], [r["msg"] for r in rows],
+                                   max_iters=MAX_ITERS)
+    assert status == [0] * len(rows)
+    for r, s, it in zip(rows, sigs, iters):
+        what = (r["kind"], r.get("value", r.get("m")), it)
+        if r["twin"]:
+            assert it == 1, what
+        else:
+            assert it == r["iters"] >= 2, what
+        assert hashlib.sha3_256(s).hexdigest() == r["sig_sha3"], what
+    assert mu == [mu_of(r["sk"], r["msg"]) for r in rows]
+    assert rows[-1]["kind"] == "edge_h" and rows[-1]["twin"] and sigs[-1][-1] == p.omega
+
+
 # ------------------------------------------------------------------ hedged Sign
 @pytest.mark.parametrize("name", NAMES)
 def test_hedged_sign(lib, ctx, sets, name):
