@@ -44,16 +44,19 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def run(lib, ctx, name, rows, context=b"", trace=True):
-    """rows: (pk, msg, sig) triples -> dict of numpy outputs.  Buffers have exactly the stated sizes."""
+def run(lib, ctx, name, rows, context=b"", trace=True, shared=None):
+    """rows: (pk, msg, sig) triples -> dict of numpy outputs.  Buffers have exactly the stated sizes.
+    shared = (buffer, offsets) replaces the rows' messages with one buffer and its len(rows) + 1 offsets."""
     import qrkem
     p = spec.PARAMS[name]
     n = len(rows)
     pk = _dev(np.frombuffer(b"".join(r[0] for r in rows), np.uint8).reshape(n, p.pk))
     sig = _dev(np.frombuffer(b"".join(r[2] for r in rows), np.uint8).reshape(n, p.sig))
-    data = b"".join(r[1] for r in rows)
+    data = b"".join(r[1] for r in rows) if shared is None else shared[0]
     msg = _dev(np.frombuffer(data, np.uint8)) if data else torch.zeros(0, dtype=torch.uint8, device="cuda")
-    off = _dev(np.cumsum([0] + [len(r[1]) for r in rows]).astype(np.uint64).view(np.int64))
+    offsets = np.cumsum([0] + [len(r[1]) for r in rows]) if shared is None else np.array(shared[1])
+    assert len(offsets) == n + 1
+    off = _dev(offsets.astype(np.uint64).view(np.int64))
     cs = _dev(np.frombuffer(context, np.uint8)) if context else None
     status = torch.full((n,), 7, dtype=torch.int32, device="cuda")
     stream = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -222,3 +225,27 @@ def test_class_agrees_with_the_abi(lib, ctx, fixture, mixed, name):
     st = s.verify_status(pk, msg, sig, offsets=off)
     assert st.is_cuda and st.dtype == torch.int32 and st.cpu().tolist() == [0 if v else -1 for v in valid]
     s.close()
+
+
+@pytest.mark.parametrize("name", SETS)
+def test_row_with_decreasing_offsets(lib, ctx, fixture, name):
+    """Three rows over one 20-byte buffer with offsets [0, 10, 5, 20]: the middle row is refused with FLAG_LONG
+    and an all-zero trace, the outer rows are verified exactly as they are alone."""
+    p, f = spec.PARAMS[name], fixture[name]
+    _, sk = spec.keygen_internal(f["xi"], name)
+    data = gold.message(name + "-offsets", 20)
+    parts = [data[:10], data[5:20]]
+    sigs = [spec.sign(sk, m) for m in parts]
+    alone = run(lib, ctx, name, [(f["pk"], m, s) for m, s in zip(parts, sigs)])
+    assert alone["status"].tolist() == [0, 0]
+    for i, (m, s) in enumerate(zip(parts, sigs)):
+        check_trace(p, alone, i, spec.verify_trace(f["pk"], m, s))
+    rows = [(f["pk"], parts[0], sigs[0]), (f["pk"], b"", sigs[0]), (f["pk"], parts[1], sigs[1])]
+    out = run(lib, ctx, name, rows, shared=(data, [0, 10, 5, 20]))
+    assert out["status"].tolist() == [0, -1, 0]
+    assert int(out["flags"][1]) == 8  # FLAG_LONG (csrc/mldsa_arith.cuh)
+    for key in ("mu", "ctilde", "w1"):
+        assert not out[key][1].any(), key
+        assert np.array_equal(out[key][[0, 2]], alone[key]), key
+    assert out["flags"][[0, 2]].tolist() == [0, 0]
+    assert run(lib, ctx, name, rows, shared=(data, [0, 10, 5, 20]), trace=False)["status"].tolist() == [0, -1, 0]

@@ -150,15 +150,18 @@ def _index(index):
     return None if index is None else _dev(np.asarray(index, dtype=np.uint32).view(np.int32))
 
 
-def verify_keyed(lib, ctx, ks, name, rows, index, context=b"", trace=True, expect=0):
-    """rows: (msg, sig) pairs -> dict of numpy outputs, as test_gpu_mldsa.run gives them for the per-row call."""
+def verify_keyed(lib, ctx, ks, name, rows, index, context=b"", trace=True, expect=0, shared=None):
+    """rows: (msg, sig) pairs -> dict of numpy outputs, as test_gpu_mldsa.run gives them for the per-row call.
+    shared = (buffer, offsets) replaces the rows' messages with one buffer and its len(rows) + 1 offsets."""
     import qrkem
     p = spec.PARAMS[name]
     n = len(rows)
     sig = _dev(np.frombuffer(b"".join(r[1] for r in rows), np.uint8).reshape(n, p.sig))
-    data = b"".join(r[0] for r in rows)
+    data = b"".join(r[0] for r in rows) if shared is None else shared[0]
     msg = _dev(np.frombuffer(data or b"\0", np.uint8))
-    off = _dev(np.cumsum([0] + [len(r[0]) for r in rows]).astype(np.uint64).view(np.int64))
+    offsets = np.cumsum([0] + [len(r[0]) for r in rows]) if shared is None else np.array(shared[1])
+    assert len(offsets) == n + 1
+    off = _dev(offsets.astype(np.uint64).view(np.int64))
     idx = _index(index)
     cs = _dev(np.frombuffer(context, np.uint8)) if context else None
     status = torch.full((n,), 7, dtype=torch.int32, device="cuda")
@@ -306,6 +309,31 @@ def test_verify_bad_indices_are_refused_rows(lib, ctx, keyed, name):
             for key in ("mu", "ctilde", "w1", "flags", "status"):
                 assert np.array_equal(got[key][i], clean[key][i]), (i, key)
     assert plain["status"].tolist() == got["status"].tolist()
+
+
+@gpu
+@pytest.mark.parametrize("name", SETS)
+def test_verify_row_with_decreasing_offsets(lib, ctx, keyed, name):
+    """As test_gpu_mldsa.test_row_with_decreasing_offsets, through the keyed call (its own copy of the offset
+    check): offsets [0, 10, 5, 20] over one 20-byte buffer, the outer rows under two different keys."""
+    f = keyed[name]
+    data = gold.message(name + "-keyed-offsets", 20)
+    parts, index = [data[:10], data[5:20]], [1, 2]
+    sigs = [spec.sign(f["sks"][k], m) for k, m in zip(index, parts)]
+    with KeySet(lib, ctx, name, f["pks"], False) as ks:
+        alone = verify_keyed(lib, ctx, ks, name, list(zip(parts, sigs)), index)
+        assert alone["status"].tolist() == [0, 0] and alone["flags"].tolist() == [0, 0]
+        same_trace(alone, per_row.run(lib, ctx, name, per_row_rows(f, list(zip(parts, sigs)), index)))
+        rows = [(parts[0], sigs[0]), (b"", sigs[0]), (parts[1], sigs[1])]
+        for trace in (True, False):
+            out = verify_keyed(lib, ctx, ks, name, rows, [1, 0, 2], trace=trace, shared=(data, [0, 10, 5, 20]))
+            assert out["status"].tolist() == [0, -1, 0]
+        out = verify_keyed(lib, ctx, ks, name, rows, [1, 0, 2], shared=(data, [0, 10, 5, 20]))
+        assert int(out["flags"][1]) == 8  # FLAG_LONG
+        for key in ("mu", "ctilde", "w1"):
+            assert not out[key][1].any(), key
+            assert np.array_equal(out[key][[0, 2]], alone[key]), key
+        assert out["flags"][[0, 2]].tolist() == [0, 0]
 
 
 @gpu

@@ -5,9 +5,10 @@ flag word, so that parity is byte-level per layer and not one boolean per row.
 
 Inputs are built once per module: one key per name and spec signatures over messages whose lengths sit on the
 padding edges of the outer hash (R || PK.seed || PK.root || M' of 55 / 56 / 63 / 64 bytes for SHA-256,
-111 / 112 / 127 / 128 for SHA-512), plus 0 and 2500.  A row of 2^31 bytes or more (FLAG_LONG) cannot be
-exercised in seconds; as for ML-DSA it stays covered by reading k_slhdsa_front and the head of
-k_slhdsa_core."""
+111 / 112 / 127 / 128 for SHA-512), plus 0 and 2500.  No row of 2^31 bytes or more goes through
+the ABI (a wrong comparison would read gibibytes from a short buffer): FLAG_LONG is reached here through a row
+whose offsets decrease, and the 2^31 threshold of row_span is pinned on the offsets alone, with no memory behind
+them, in tests/test_gpu_slhdsa_prims.py."""
 import ctypes as ct
 import hashlib
 
@@ -77,16 +78,19 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def run(lib, ctx, name, rows, context=b"", trace=True):
-    """rows: (pk, msg, sig) triples -> dict of numpy outputs.  Buffers have exactly the stated sizes."""
+def run(lib, ctx, name, rows, context=b"", trace=True, shared=None):
+    """rows: (pk, msg, sig) triples -> dict of numpy outputs.  Buffers have exactly the stated sizes.
+    shared = (buffer, offsets) replaces the rows' messages with one buffer and its len(rows) + 1 offsets."""
     import qrkem
     p = spec.PARAMS[name]
     n = len(rows)
     pk = _dev(np.frombuffer(b"".join(r[0] for r in rows), np.uint8).reshape(n, p.pk))
     sig = _dev(np.frombuffer(b"".join(r[2] for r in rows), np.uint8).reshape(n, p.sig))
-    data = b"".join(r[1] for r in rows)
+    data = b"".join(r[1] for r in rows) if shared is None else shared[0]
     msg = _dev(np.frombuffer(data, np.uint8)) if data else torch.zeros(0, dtype=torch.uint8, device="cuda")
-    off = _dev(np.cumsum([0] + [len(r[1]) for r in rows]).astype(np.uint64).view(np.int64))
+    offsets = np.cumsum([0] + [len(r[1]) for r in rows]) if shared is None else np.array(shared[1])
+    assert len(offsets) == n + 1
+    off = _dev(offsets.astype(np.uint64).view(np.int64))
     cs = _dev(np.frombuffer(context, np.uint8)) if context else None
     status = torch.full((n,), 7, dtype=torch.int32, device="cuda")
     stream = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -300,3 +304,26 @@ def test_class_agrees_with_the_abi(lib, ctx, signed, mixed, name):
     st = s.verify_status(pk, msg, sig, offsets=off)
     assert st.is_cuda and st.dtype == torch.int32 and st.cpu().tolist() == [0 if v else -1 for v in valid]
     s.close()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_row_with_decreasing_offsets(lib, ctx, fixture, name):
+    """Three rows over one 20-byte buffer with offsets [0, 10, 5, 20]: the middle row is refused with FLAG_LONG
+    and an all-zero trace, the outer rows are verified exactly as they are alone."""
+    f = fixture[name]
+    data = gold.message(name + "-offsets", 20)
+    parts = [data[:10], data[5:20]]
+    sigs = [spec.sign(name, f["sk"], m) for m in parts]
+    alone = run(lib, ctx, name, [(f["pk"], m, s) for m, s in zip(parts, sigs)])
+    assert alone["status"].tolist() == [0, 0]
+    for i, (m, s) in enumerate(zip(parts, sigs)):
+        check_trace(alone, i, spec.verify_trace(name, f["pk"], m, s))
+    rows = [(f["pk"], parts[0], sigs[0]), (f["pk"], b"", sigs[0]), (f["pk"], parts[1], sigs[1])]
+    out = run(lib, ctx, name, rows, shared=(data, [0, 10, 5, 20]))
+    assert out["status"].tolist() == [0, -1, 0]
+    assert int(out["flags"][1]) == spec.FLAG_LONG == 2
+    for key in ("digest", "fors_pk", "roots"):
+        assert not out[key][1].any(), key
+        assert np.array_equal(out[key][[0, 2]], alone[key]), key
+    assert out["flags"][[0, 2]].tolist() == [0, 0]
+    assert run(lib, ctx, name, rows, shared=(data, [0, 10, 5, 20]), trace=False)["status"].tolist() == [0, -1, 0]

@@ -3,8 +3,10 @@ qrk_sig_sign_batch, csrc/slhdsa_sign.hip) against tests/slhdsa_spec.py, tests/go
 tests/golden/slhdsa_sign.json.  Deterministic signatures are compared byte for byte through their stored
 SHA3-256 (and located through the stored part hashes); everything else is checked through R = PRF_msg (cheap
 in the spec), through qrk_sig_verify_batch, and for one row per test through the spec's verifier.  The spec
-signs nothing here: one signature costs it 0.2 to 0.7 s.  A row of 2^31 bytes or more cannot be exercised in
-seconds; FLAG_LONG is reached through a row whose offsets decrease."""
+signs nothing here: one signature costs it 0.2 to 0.7 s.  No row of 2^31 bytes or more goes
+through the ABI (a wrong comparison would read gibibytes from a short buffer): FLAG_LONG is reached here through a
+row whose offsets decrease, and the 2^31 threshold of row_span is pinned on the offsets alone, with no memory
+behind them, in tests/test_gpu_slhdsa_prims.py."""
 import ctypes as ct
 import hashlib
 
