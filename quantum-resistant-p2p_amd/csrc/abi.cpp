@@ -173,12 +173,7 @@ struct qrk_ctx {
   uint8_t* hio_dev = nullptr;     // device mapping of hio (zero-copy small calls)
   uint32_t* hflag = nullptr;      // single-shot completion flag (fine-grained pinned) ...
   uint32_t* hflag_dev = nullptr;  // ... its device address
-  uint32_t* kg_cnt = nullptr;     // multi-workgroup ML-KEM KeyGen arrival counters (zeroed at allocation)
-  bool kg_dirty = false;          // a pipelined KeyGen failed: a straggler may have set a flag word
-                                  // after the collector's reset, or stored scratch after its wipe
-  uint32_t* fixc = nullptr;       // ML-KEM SampleNTT fix-up counters of chunks <= 2^15 (Streams::fixc)
-  int fixp = 0;                   // the counter the next such chunk counts into
-  bool fixc_dirty = false;        // a chunk's launches failed after the parity flip: re-zero both
+  mlkem::CtxState mlkem;          // what ML-KEM alone keeps between calls (qrkem_internal.h)
   uint32_t ticket = 0;            // what the last single-shot call asked its kernel to store in hflag[0]
   hipStream_t io_stream = nullptr;
   int streams = 0;            // 0: multi-role launches, 1: serial (one kernel per launch)
@@ -289,8 +284,6 @@ static const AlgInfo* resolve(const char* alg) {
   return nullptr;
 }
 
-enum class Op { KEYPAIR, ENCAPS, DECAPS };
-
 // What one caller asks of one run_batch call beyond the batch itself.  Each option takes effect
 // only where run_batch says so; the public device-pointer entry points pass none.
 struct CallOpts {
@@ -394,15 +387,6 @@ static const uint8_t* stage_os_random(qrk_ctx* ctx, size_t bytes, hipStream_t st
   return ctx->dstage;
 }
 
-// Queues, on `st`, the re-zero of what a failed pipelined ML-KEM KeyGen may have left behind
-// (qrk_ctx::kg_dirty): its flag words and the head of the scratch its workgroups store to.
-static hipError_t kg_rezero(qrk_ctx* ctx, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(ctx->kg_cnt, 0, mlkem_kg_flag_words() * sizeof(uint32_t), st);
-  if (e == hipSuccess && ctx->scratch)
-    e = hipMemsetAsync(ctx->scratch, 0, std::min(ctx->scratch_bytes, mlkem_kg_scratch_bytes()), st);
-  return e;
-}
-
 // Core batched driver over device pointers, chunked.
 static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o1, uint8_t* o2, const uint8_t* i1,
                      const uint8_t* i2, int32_t* status, hipStream_t st, const CallOpts& opts) {
@@ -432,37 +416,13 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     S.ticket = ctx->ticket;
     S.host_in1 = opts.host_in1;
   }
-  if (a.family == Family::MLKEM && op == Op::KEYPAIR && n <= mlkem_kg_multi_max()) {
-    if (!ctx->kg_cnt) {
-      hipError_t e = hipMalloc((void**)&ctx->kg_cnt, mlkem_kg_flag_words() * sizeof(uint32_t));
-      if (e == hipSuccess) e = hipMemset(ctx->kg_cnt, 0, mlkem_kg_flag_words() * sizeof(uint32_t));
-      if (e != hipSuccess) return hip_fail("hipMalloc(kg_cnt)", e);
-    }
-    if (ctx->kg_dirty) {  // stream-ordered behind the failed call's kernel
-      const hipError_t e = kg_rezero(ctx, st);
-      if (e != hipSuccess) return hip_fail("hipMemsetAsync(kg_cnt)", e);
-      ctx->kg_dirty = false;
-    }
-    S.kg_cnt = ctx->kg_cnt;
+  if (a.family == Family::MLKEM) {
     if (opts.kg_err) S.kg_err = ctx->hflag_dev + 1;
-  }
-  if (a.family == Family::MLKEM && n <= chunk && n > mlkem_small_max()) {
-    S.xof_keep = op == Op::KEYPAIR ? opts.xof_keep : nullptr;
-    S.xof_given = op == Op::DECAPS ? opts.xof_given : nullptr;
-  }
-  if (a.family == Family::MLKEM && op != Op::KEYPAIR) {
-    if (!ctx->fixc) {
-      hipError_t e = hipMalloc((void**)&ctx->fixc, 2 * sizeof(uint32_t));
-      if (e == hipSuccess) e = hipMemset(ctx->fixc, 0, 2 * sizeof(uint32_t));
-      if (e != hipSuccess) return hip_fail("hipMalloc(fixc)", e);
-    }
-    if (ctx->fixc_dirty) {
-      const hipError_t e = hipMemsetAsync(ctx->fixc, 0, 2 * sizeof(uint32_t), st);
-      if (e != hipSuccess) return hip_fail("hipMemsetAsync(fixc)", e);
-      ctx->fixc_dirty = false;
-    }
-    S.fixc = ctx->fixc;
-    S.fixp = &ctx->fixp;
+    S.xof_keep = opts.xof_keep;
+    S.xof_given = opts.xof_given;
+    const char* what = nullptr;
+    const hipError_t e = ctx->mlkem.prepare(S, op, n, chunk, ctx->scratch, ctx->scratch_bytes, &what);
+    if (e != hipSuccess) return hip_fail(what, e);
   }
   HT(3);
   for (size_t off = 0; off < n; off += chunk) {
@@ -488,7 +448,7 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     }
     HT(4);
     if (e != hipSuccess) {
-      ctx->fixc_dirty = S.fixc != nullptr;  // the counters' zero-between-calls invariant is unknown now
+      ctx->mlkem.chunk_failed(S);  // whatever the family: S carries no ML-KEM counters for the others
       return hip_fail("kernel launch", e);
     }
     // key material of this chunk (seeds, m', K', Kbar, ...) does not outlive the call
@@ -620,19 +580,14 @@ static int run_small_host(qrk_ctx* ctx, const AlgInfo& a, Op op, const IoLayout&
   // synchronise waited for)
   if (!rc && opts.kg_err && __atomic_load_n(ctx->hflag + 1, __ATOMIC_ACQUIRE) != 0)
     rc = fail("ML-KEM KeyGen: keygen hand-off timeout (a bounded cross-workgroup wait expired)");
-  if (rc && opts.kg_err) ctx->kg_dirty = true;  // re-zeroed (flags, scratch) before the next KeyGen launch
   if (!rc) {
     memcpy(o1, h + L.o_o1, n * L.l_o1);
     if (L.l_o2) memcpy(o2, h + L.o_o2, n * L.l_o2);
     if (status) memcpy(status, h + L.o_st, n * L.l_st);
   }
-  if (rc) (void)hipStreamSynchronize(st);  // nothing may still read or write the mirror
-  if (rc && ctx->kg_dirty && ctx->kg_cnt) {
-    // wipe the secret scratch a straggler may have written after the collector's wipe now, not at
-    // the next KeyGen (run_batch re-zeroes again if this fails)
-    hipError_t w = kg_rezero(ctx, st);
-    if (w == hipSuccess) w = hipStreamSynchronize(st);
-    if (w == hipSuccess) ctx->kg_dirty = false;
+  if (rc) {
+    (void)hipStreamSynchronize(st);  // nothing may still read or write the mirror
+    ctx->mlkem.keygen_failed(opts.kg_err, ctx->scratch, ctx->scratch_bytes, st);
   }
   OQS_MEM_cleanse(h, L.total);  // coins, secret keys and shared secrets do not outlive the call
   HT(7);
@@ -888,8 +843,7 @@ void qrk_ctx_destroy(qrk_ctx* ctx) {
   if (ctx->io_stream) (void)hipStreamDestroy(ctx->io_stream);
   if (ctx->dstage) (void)hipFree(ctx->dstage);
   if (ctx->hstage) (void)hipHostFree(ctx->hstage);
-  if (ctx->kg_cnt) (void)hipFree(ctx->kg_cnt);
-  if (ctx->fixc) (void)hipFree(ctx->fixc);
+  ctx->mlkem.free();
   if (ctx->ev_up) (void)hipEventDestroy(ctx->ev_up);
   if (ctx->ev_last) (void)hipEventDestroy(ctx->ev_last);
   delete ctx;
@@ -958,11 +912,9 @@ extern "C" int qrk_dbg_fail_after_flip(int on) {
 extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
   CallScope scope;
   if (open_inspect(scope, ctx, out && parity)) return -1;
-  out[0] = out[1] = 0;
-  *parity = ctx->fixp;
-  if (!ctx->fixc) return 0;
-  const hipError_t e = hipMemcpy(out, ctx->fixc, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  return e == hipSuccess ? 0 : hip_fail("hipMemcpy(fixc)", e);
+  const char* what = nullptr;
+  const hipError_t e = ctx->mlkem.fix_words(out, parity, &what);
+  return e == hipSuccess ? 0 : hip_fail(what, e);
 }
 
 // Tests only (not in qrkem.h): nonzero words among the context's single-shot KeyGen flag / counter
@@ -970,11 +922,7 @@ extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
 extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
   CallScope scope;
   if (open_inspect(scope, ctx, out)) return -1;
-  *out = 0;
-  if (!ctx->kg_cnt) return 0;
-  std::vector<uint32_t> tmp(mlkem_kg_flag_words());
-  const hipError_t e = hipMemcpy(tmp.data(), ctx->kg_cnt, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  for (uint32_t x : tmp) *out += x != 0;
+  const hipError_t e = ctx->mlkem.kg_flags_residue(out);
   return e == hipSuccess ? 0 : hip_fail("hipMemcpy(kg flags)", e);
 }
 

@@ -1,5 +1,5 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
-// launchers (mlkem.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
+// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -86,7 +86,7 @@ void mlkem_records_span(const AlgInfo& a, size_t C, size_t* off, size_t* bytes);
 size_t mlkem_small_max();
 // ML-KEM KeyGen batches up to this size run one workgroup per SampleNTT / PRF item (latency)
 size_t mlkem_kg_multi_max();
-// flag / counter words of the single-shot multi-workgroup KeyGen (ctx->kg_cnt)
+// flag / counter words of the single-shot multi-workgroup KeyGen (mlkem::CtxState, Streams::kg_cnt)
 size_t mlkem_kg_flag_words();
 // bytes of the batched sampled matrix of a chunk of `chunk` handshakes (Streams::xof_keep)
 size_t mlkem_matrix_bytes(const AlgInfo& a, size_t chunk);
@@ -107,8 +107,9 @@ hipError_t hqc_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st
 struct Streams {
   hipStream_t main = nullptr;
   // serial schedule: one kernel per launch (per-kernel timings in isolation); otherwise
-  // independent kernels of one operation share multi-role launches (ML-KEM, mlkem.hip)
+  // independent kernels of one operation share multi-role launches (ML-KEM, mlkem_batch.cuh)
   bool serial = false;
+  // ---- ML-KEM only, from here to the end of the struct (FrodoKEM and HQC read none of it)
   // single-shot completion flag (fine-grained host memory, device address): the one-launch ML-KEM
   // kernels store `ticket` there once their outputs are visible to the host
   uint32_t* done = nullptr;
@@ -126,8 +127,8 @@ struct Streams {
   const uint8_t* host_in1 = nullptr;
   // batched ML-KEM Encaps / Decaps at chunks <= 2^15: the context's two SampleNTT fix-up counters
   // (device, zero at allocation) and which one the next call counts into (host; the call flips it
-  // and its first launch zeroes the other word, mlkem.hip rho_source).  Set only by run_batch, which
-  // re-zeroes both words after any failed chunk (qrk_ctx::fixc_dirty).
+  // and its first launch zeroes the other word, mlkem_batch.cuh rho_source).  Set only by
+  // mlkem::CtxState::prepare, which re-zeroes both words after any failed chunk.
   uint32_t* fixc = nullptr;
   int* fixp = nullptr;
   // batched ML-KEM (one chunk, n > mlkem_small_max()), the handshake driver's expanded-key reuse:
@@ -137,6 +138,42 @@ struct Streams {
   uint64_t* xof_keep = nullptr;
   const uint64_t* xof_given = nullptr;
 };
+
+enum class Op { KEYPAIR, ENCAPS, DECAPS };
+
+// What a context keeps for ML-KEM alone between calls (a member of qrk_ctx; functions and the
+// invariants they keep in mlkem_batch.cuh, beside rho_source).  The driver calls these under the
+// context lock and touches no field.
+namespace mlkem {
+struct CtxState {
+  // Before the chunks of a call of n handshakes (chunks of `chunk`) on S.main: allocates what the call
+  // needs on first use, queues the re-zero an earlier failure left owing, and sets S.kg_cnt, S.fixc and
+  // S.fixp.  S.kg_err, S.xof_keep and S.xof_given come in as the caller was asked for them and are
+  // cleared where they do not apply to this call.  scratch: the context's.  On failure *what names
+  // the step.
+  hipError_t prepare(Streams& S, Op op, size_t n, size_t chunk, void* scratch, size_t scratch_bytes,
+                     const char** what);
+  // a chunk failed after prepare()
+  void chunk_failed(const Streams& S);
+  // a zero-copy host call on `st` failed and the stream is idle; pipe_call: it was a KeyGen that handed
+  // out the error word
+  void keygen_failed(bool pipe_call, void* scratch, size_t scratch_bytes, hipStream_t st);
+  void free();
+  // tests (qrk_dbg_fixc_words, qrk_dbg_kg_flags_residue): the two fix-up counters and the parity;
+  // nonzero words among the KeyGen flag words.  On failure *what names the step.
+  hipError_t fix_words(uint32_t* out, int* parity, const char** what) const;
+  hipError_t kg_flags_residue(uint64_t* out) const;
+
+ private:
+  hipError_t kg_rezero(void* scratch, size_t scratch_bytes, hipStream_t st);
+  uint32_t* kg_cnt = nullptr;  // single-shot KeyGen arrival counters / flag words (mlkem_kg_flag_words)
+  bool kg_dirty = false;       // a pipelined KeyGen failed: a straggler may have set a flag word
+                               // after the collector's reset, or stored scratch after its wipe
+  uint32_t* fixc = nullptr;    // SampleNTT fix-up counters of chunks <= 2^15 (Streams::fixc)
+  int fixp = 0;                // the counter the next such chunk counts into
+  bool fixc_dirty = false;     // a chunk's launches failed after the parity flip: re-zero both
+};
+}  // namespace mlkem
 
 // All pointers are device pointers; n handshakes processed as one chunk
 // (the caller splits large batches).  Return hipError_t.  The three families share one signature

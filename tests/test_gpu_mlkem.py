@@ -470,3 +470,54 @@ def test_fixup_counters_rezeroed_after_failed_chunk(op):
     else:
         assert np.array_equal(ss[idx], orc.batch_decaps(alg, sk[idx], np.ascontiguousarray(ct_[idx])))
     eng.close()
+
+
+def test_context_state_interleaved_keygen_and_direct_rho():
+    """One context's ML-KEM state across the two things it holds, interleaved: the single-shot KeyGen
+    flag words (a host-pointer KeyGen of 16: k_keygen_pipe; a device-pointer one: k_keygen_multi, same
+    words) and the SampleNTT fix-up counter pair (device-pointer Encaps, then Decaps, of 1088: the
+    direct-rho path, parity 0 -> 1 -> 0).  Every output byte-exact vs the oracle; the flag words all
+    zero after every step; after the last, parity 0 and the counter the next call counts into zero."""
+    import ctypes as ct
+    import oracle as orc
+    from qrkem._native import LIB
+    from qrkem.batch import BatchKEM
+    alg, n_kg, n = "ML-KEM-512", 16, 1088
+    res = LIB.qrk_dbg_kg_flags_residue
+    res.argtypes, res.restype = [ct.c_void_p, ct.POINTER(ct.c_uint64)], ct.c_int
+    words = LIB.qrk_dbg_fixc_words
+    words.argtypes, words.restype = [ct.c_void_p, ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_int)], ct.c_int
+    eng = BatchKEM(alg, device=0)
+
+    def flags_clear():
+        cnt = ct.c_uint64(1)
+        assert res(eng._ctx, ct.byref(cnt)) == 0
+        return cnt.value == 0
+
+    coins = orc.bench_coins(n, 96, seed=4242)
+    kc, ec = np.ascontiguousarray(coins[:, :64]), np.ascontiguousarray(coins[:, 64:])
+    opk, osk = orc.batch_keypair(alg, kc)
+    oct_, oss = orc.batch_encaps(alg, opk, ec)
+    kg1, kg3 = (np.ascontiguousarray(orc.bench_coins(n_kg, 64, seed=s)) for s in (4243, 4244))
+    # 1: host-pointer KeyGen
+    pk1, sk1 = eng.keypair(coins=kg1)
+    o1 = orc.batch_keypair(alg, kg1)
+    assert np.array_equal(pk1, o1[0]) and np.array_equal(sk1, o1[1])
+    assert flags_clear()
+    # 2: device-pointer Encaps
+    ct2, ss2 = eng.encaps(_dev(opk), coins=_dev(ec))
+    assert np.array_equal(_host(ct2), oct_) and np.array_equal(_host(ss2), oss)
+    assert flags_clear()
+    # 3: device-pointer KeyGen
+    pk3, sk3 = eng.keypair(coins=_dev(kg3))
+    o3 = orc.batch_keypair(alg, kg3)
+    assert np.array_equal(_host(pk3), o3[0]) and np.array_equal(_host(sk3), o3[1])
+    assert flags_clear()
+    # 4: device-pointer Decaps
+    assert np.array_equal(_host(eng.decaps(_dev(osk), _dev(oct_))), oss)
+    assert flags_clear()
+    w = (ct.c_uint32 * 2)()
+    par = ct.c_int(-1)
+    assert words(eng._ctx, w, ct.byref(par)) == 0
+    assert par.value == 0 and w[0] == 0, (par.value, w[0], w[1])
+    eng.close()

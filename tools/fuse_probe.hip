@@ -1,4 +1,4 @@
-// Multi-role launches (mlkem.hip k_pair / k_seq): which grouping of the batched ML-KEM-768 Encaps /
+// Multi-role launches (mlkem_batch.cuh k_pair / k_seq): which grouping of the batched ML-KEM-768 Encaps /
 // Decaps kernels is fastest at 2^20, 2^18, 2^16 and 2^14 handshakes.  Every variant is the whole launch
 // sequence of one call after the rho copy; hipEvent timing of 10 back-to-back calls, 5 rounds with
 // the variants interleaved, after a warm-up that brings the clocks up; the median round is printed.
@@ -16,7 +16,7 @@
 //   D_d            seq(J, dec, xof); G; seq(fix, prf); core
 //   D_e            seq(J, dec, xof); pair(G, fix); prf; core
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/fuse_probe.hip -o tools/fuse_probe
-#include "../quantum-resistant-p2p_amd/csrc/mlkem.hip"
+#include "../quantum-resistant-p2p_amd/csrc/mlkem_batch.cuh"
 
 #include <algorithm>
 #include <cstdio>
@@ -27,6 +27,11 @@
 namespace qrk {
 thread_local KernelTimer* g_timer = nullptr;
 thread_local hipError_t g_launch_err = hipSuccess;
+// sizes of the paths this probe leaves out, for mlkem::CtxState (never used here: no context)
+size_t mlkem_small_max() { return 1024; }
+size_t mlkem_kg_multi_max() { return 0; }
+size_t mlkem_kg_flag_words() { return 0; }
+size_t mlkem_kg_scratch_bytes() { return 0; }
 }  // namespace qrk
 using namespace qrk;
 using namespace qrk::mlkem;
@@ -55,7 +60,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(A::WPE > B:
   else
     a.run((uint32_t)w - tb, lds);
 }
-// role A takes workgroups [0, a.nb), role B the rest (as mlkem.hip k_multi)
+// role A takes workgroups [0, a.nb), role B the rest (as mlkem_batch.cuh k_multi)
 template <class A, class B>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(A::WPE > B::WPE ? A::WPE : B::WPE))) void k_seq(
     A a, B b) {

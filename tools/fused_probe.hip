@@ -2,10 +2,10 @@
 // "measure a fused, wave-specialised SampleNTT -> encrypt-core kernel that keeps A-hat on chip").
 //
 // k_fused<T, NP, NB>: one persistent workgroup per CU.  Waves 0 .. NP-1 are producers (lane-per-entry
-// SHAKE128 with the product's per-lane LDS ring compaction, mlkem.hip compact_block, but the 12-bit
+// SHAKE128 with the product's per-lane LDS ring compaction, mlkem_sample.cuh compact_block, but the 12-bit
 // chunks go to an LDS ring of row-tiles instead of HBM); the other T / 4 waves are consumers, one
 // 16-lane group per handshake of a T-handshake tile, running the product's encrypt core
-// (mlkem.hip encrypt_core_hs) with the matrix rows read from that ring.  The matrix is streamed one
+// (mlkem_batch.cuh encrypt_core_hs) with the matrix rows read from that ring.  The matrix is streamed one
 // row at a time: row-tile r = (tile, row i) holds A[j][i] = SampleNTT(rho || i || j) for the K
 // columns j of the T handshakes (K T entries, 384 B each at a 392-B stride).  A producer round fills
 // 64 NP / (K T) row-tiles; NB row-tile buffers form the ring.  Hand-off by monotonic LDS counters:
@@ -24,9 +24,9 @@
 // SampleNTT role with its workgroups padded to 1..5 per CU (4..20 waves per CU).
 //
 // Baseline: the product's serial launches k_xof (SampleNTT, 3 blocks), k_xof_fix, k_encrypt_core on
-// the same 2^20-handshake ML-KEM-768 chunk; reference ciphertexts from mlkem.hip encaps_impl.
+// the same 2^20-handshake ML-KEM-768 chunk; reference ciphertexts from mlkem_batch.cuh encaps_impl.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/fused_probe.hip -o tools/fused_probe
-#include "../quantum-resistant-p2p_amd/csrc/mlkem.hip"
+#include "../quantum-resistant-p2p_amd/csrc/mlkem_batch.cuh"
 
 #include <algorithm>
 #include <cstdio>
@@ -38,6 +38,11 @@
 namespace qrk {
 thread_local KernelTimer* g_timer = nullptr;
 thread_local hipError_t g_launch_err = hipSuccess;
+// sizes of the paths this probe leaves out, for mlkem::CtxState (never used here: no context)
+size_t mlkem_small_max() { return 1024; }
+size_t mlkem_kg_multi_max() { return 0; }
+size_t mlkem_kg_flag_words() { return 0; }
+size_t mlkem_kg_scratch_bytes() { return 0; }
 }  // namespace qrk
 using namespace qrk;
 using namespace qrk::mlkem;
@@ -65,7 +70,7 @@ __device__ __forceinline__ void signal(uint32_t* c) {
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// ---- producer: the product's compaction (mlkem.hip compact_block) into an LDS entry
+// ---- producer: the product's compaction (mlkem_sample.cuh compact_block) into an LDS entry
 struct PendL {
   uint32_t r[8];
   int ch = -1;
@@ -110,7 +115,7 @@ __device__ __forceinline__ void compact_l(const KState& s, char* ring_all, uint3
   }
 }
 
-// ---- consumer: mlkem.hip encrypt_core_hs (MODE 0) with the matrix rows from the LDS ring
+// ---- consumer: mlkem_batch.cuh encrypt_core_hs (MODE 0) with the matrix rows from the LDS ring
 template <int T, int NP, int NB>
 __device__ __forceinline__ void load_row(const char* ringb, uint32_t* fullc, uint32_t* freec, int r, int g, int L,
                                          PK8 an[KK]) {

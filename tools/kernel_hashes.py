@@ -6,7 +6,8 @@
 Compiles every csrc/*.hip device-only for gfx950 (the Makefile's flags), disassembles the code
 objects and hashes each function's instruction text (addresses and branch-target labels
 normalised), so a source clean-up can be shown to leave every remaining kernel bit-identical.
-Compare two runs with `tools/kernel_hashes.py --diff A.json B.json`.
+Compare two runs with `tools/kernel_hashes.py --diff A.json B.json`, or, when code moved between files,
+with `--diff-by-name` (function names alone; a name with two different hashes in one run is an error).
 """
 import hashlib
 import json
@@ -55,10 +56,24 @@ def functions(co):
     return {k: hashlib.sha256("\n".join(v).encode()).hexdigest()[:16] for k, v in out.items()}
 
 
+def by_name(res, path):
+    """file:function -> function, for comparing across a move of code between files.  A name may repeat
+    (a header template instantiated in two files) only with one hash; anything else ends the run."""
+    out, where = {}, {}
+    for k, h in res.items():
+        f, name = k.split(":", 1)
+        if out.setdefault(name, h) != h:
+            sys.exit(f"{path}: {name} differs between {where[name]} and {f}")
+        where[name] = f
+    return out
+
+
 def main():
     a = sys.argv[1:]
-    if a and a[0] == "--diff":
+    if a and a[0] in ("--diff", "--diff-by-name"):
         x, y = json.load(open(a[1])), json.load(open(a[2]))
+        if a[0] == "--diff-by-name":
+            x, y = by_name(x, a[1]), by_name(y, a[2])
         same = sorted(k for k in x if k in y and x[k] == y[k])
         changed = sorted(k for k in x if k in y and x[k] != y[k])
         gone = sorted(k for k in x if k not in y)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-candidate instruction budget of SampleNTT's compaction (compact_block, mlkem.hip), from the
+"""Per-candidate instruction budget of SampleNTT's compaction (compact_block, mlkem_sample.cuh), from the
 gfx950 disassembly of the serial k_xof kernel.
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S csrc/mlkem.hip -o mlkem.s

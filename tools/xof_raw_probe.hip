@@ -3,7 +3,7 @@
 // acceptance and compaction out of k_xof, measured rather than estimated").
 //
 // Four kernels over the 2^20-handshake ML-KEM-768 matrix (9 entries per handshake):
-//   ring   the product's SampleNTT role (mlkem.hip RXof, included as-is): 3 blocks, 12-bit chunk
+//   ring   the product's SampleNTT role (mlkem_batch.cuh RXof, included as-is): 3 blocks, 12-bit chunk
 //          pairs written by the per-lane LDS ring compaction
 //   raw    3 blocks, the 504 squeezed bytes stored as 63 tiled u64 words + an 11-dword acceptance
 //          mask (one v_cmp + one v_addc per candidate, bit-reversed per dword at the end)
@@ -15,7 +15,7 @@
 // ring + load is the shipped pipeline's SampleNTT cost, raw + place the proposed one (fix-up
 // entries, ~0.7 %, are excluded from the comparison of the two outputs, which must be equal).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/xof_raw_probe.hip -o xof_raw_probe
-#include "../quantum-resistant-p2p_amd/csrc/mlkem.hip"
+#include "../quantum-resistant-p2p_amd/csrc/mlkem_batch.cuh"
 
 #include <algorithm>
 #include <cstdio>
@@ -24,6 +24,11 @@
 namespace qrk {
 thread_local KernelTimer* g_timer = nullptr;
 thread_local hipError_t g_launch_err = hipSuccess;
+// sizes of the paths this probe leaves out, for mlkem::CtxState (never used here: no context)
+size_t mlkem_small_max() { return 1024; }
+size_t mlkem_kg_multi_max() { return 0; }
+size_t mlkem_kg_flag_words() { return 0; }
+size_t mlkem_kg_scratch_bytes() { return 0; }
 }  // namespace qrk
 using namespace qrk;
 using namespace qrk::mlkem;
@@ -84,7 +89,7 @@ struct Pk8Out {
   uint4 a, b;
 };
 
-// the product's consumer read (mlkem.hip load_sampled on the packed 12-bit layout)
+// the product's consumer read (mlkem_poly.cuh load_sampled on the packed 12-bit layout)
 __global__ __launch_bounds__(256) void k_load(const uint64_t* __restrict__ xof, size_t nent, Pk8Out* __restrict__ out) {
   const size_t e = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const int L = threadIdx.x & 15;
