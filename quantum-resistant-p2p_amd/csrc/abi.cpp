@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/qrkem.h"
+#include "qrkem_debug.h"
 #include "qrkem_internal.h"
 
 // -DQRK_HOST_TRACE=1 (tools/build_variant.sh builds only): steady-clock stamps at the phases of a
@@ -27,7 +28,7 @@
 #if QRK_HOST_TRACE
 static long long g_host_trace[16];
 #define HT(i) (g_host_trace[i] = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count())
-extern "C" int qrk_dbg_host_trace(long long* out) {
+int qrk_dbg_host_trace(long long* out) {
   memcpy(out, g_host_trace, sizeof(g_host_trace));
   return 0;
 }
@@ -885,31 +886,23 @@ int qrk_ctx_staging_residue(qrk_ctx* ctx, uint64_t out[3]) {
   return 0;
 }
 
-// Tests only (not in qrkem.h): the workgroup of role `role` of the pipelined single-shot ML-KEM KeyGen
-// (PRF item N = role < 2K, row r = role - 2K + 1) publishes its payload and flags 150 ms late, past
-// every bounded wait (-1: off).  Process-wide.
-extern "C" int qrk_dbg_kg_late(int role) {
+// ---- test hooks: declared and documented in qrkem_debug.h, not in qrkem.h
+int qrk_dbg_kg_late(int role) {
   g_kg_dbg_late.store(role, std::memory_order_relaxed);
   return 0;
 }
 
-// Tests only (not in qrkem.h): every ABI call (every chunk of a chunked one) fails as if its first
-// launch had been rejected (0: off): launch_begin() records hipErrorLaunchFailure.  The kernels
-// themselves still launch, on valid buffers, except where a launcher stops at the first failure.
-// Process-wide.
-extern "C" int qrk_dbg_fail_launch(int on) {
+int qrk_dbg_fail_launch(int on) {
   g_dbg_fail_launch.store(on, std::memory_order_relaxed);
   return 0;
 }
 
-// Tests only (not in qrkem.h): batched ML-KEM Encaps / Decaps chunks of at most 2^15 handshakes fail
-// right after the SampleNTT fix-up counter parity flip, before their first launch (0: off), and the
-// context's two fix-up counter words and its parity read back (the re-zero path).
-extern "C" int qrk_dbg_fail_after_flip(int on) {
+int qrk_dbg_fail_after_flip(int on) {
   g_dbg_fail_after_flip.store(on, std::memory_order_relaxed);
   return 0;
 }
-extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
+
+int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
   CallScope scope;
   if (open_inspect(scope, ctx, out && parity)) return -1;
   const char* what = nullptr;
@@ -917,18 +910,14 @@ extern "C" int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity) {
   return e == hipSuccess ? 0 : hip_fail(what, e);
 }
 
-// Tests only (not in qrkem.h): nonzero words among the context's single-shot KeyGen flag / counter
-// words, which must be zero between calls (after a failed pipelined KeyGen too).
-extern "C" int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
+int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out) {
   CallScope scope;
   if (open_inspect(scope, ctx, out)) return -1;
   const hipError_t e = ctx->mlkem.kg_flags_residue(out);
   return e == hipSuccess ? 0 : hip_fail("hipMemcpy(kg flags)", e);
 }
 
-// Tests only (not in qrkem.h): nonzero bytes left in the ML-KEM per-handshake records of a chunk
-// of n handshakes (mlkem_cleanse wipes them after every chunk).
-extern "C" int qrk_dbg_mlkem_records_residue(qrk_ctx* ctx, const char* alg, size_t n, uint64_t* out) {
+int qrk_dbg_mlkem_records_residue(qrk_ctx* ctx, const char* alg, size_t n, uint64_t* out) {
   CallScope scope;
   if (open_inspect(scope, ctx, out)) return -1;
   const AlgInfo* a = find_alg(alg);
@@ -1241,19 +1230,16 @@ int qrk_aead_open_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   return e == hipSuccess ? 0 : hip_fail("aead_open", e);
 }
 
-// Tests only (not in qrkem.h): Poly1305 and GHASH on chosen keys.  Through the AEADs r, s and H are
-// cipher outputs and cannot be steered to their edge cases (r = 1 with an accumulator of exactly p + k,
-// single-bit and all-ones H).  Device pointers; tag_i = Poly1305(key32_i = r | s, msg_i), msg ragged by
-// msg_off [n+1]; out_i = GHASH_{h_i}(data_i), data_i a whole number of 16-byte blocks.
-extern "C" int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off,
-                                      uint8_t* tag, void* stream) {
+// test hooks (qrkem_debug.h): Poly1305 and GHASH on chosen keys
+int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off, uint8_t* tag,
+                           void* stream) {
   if (n && (!key32 || !msg || !msg_off || !tag)) return fail("null buffer");
   launch_begin();  // no context, so no scope
   hipError_t e = dbg_poly1305(n, key32, msg, msg_off, tag, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail("dbg_poly1305", e);
 }
-extern "C" int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off,
-                                   uint8_t* out, void* stream) {
+int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
+                        void* stream) {
   if (n && (!h || !data || !data_off || !out)) return fail("null buffer");
   launch_begin();
   hipError_t e = dbg_ghash(n, h, data, data_off, out, (hipStream_t)stream);
@@ -1416,28 +1402,20 @@ int qrk_mldsa_sign_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t*
                          nullptr, nullptr, (hipStream_t)stream);
 }
 
-// Tests only (not in qrkem.h): qrk_mldsa_sign_batch with the loop's cap as an argument, which also writes, per row,
-// mu [n][64] (zeros for a row refused for its offsets or length) and the iterations run, iters [n] (0 for a refused
-// row, max_iters for one that exhausted them).  The production kernel stores them itself, in an instantiation no
-// other call launches; this is what pins the rejection loop against tests/mldsa_spec.py iteration by iteration,
-// and what lets a test reach the cap.
-extern "C" int qrk_dbg_mldsa_sign_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
-                                        const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str,
-                                        size_t ctx_len, uint8_t* sig, int32_t* status, uint32_t max_iters, uint8_t* mu,
-                                        uint32_t* iters, void* stream) {
+// test hook (qrkem_debug.h): the call above with the loop's cap as an argument and the trace outputs
+int qrk_dbg_mldsa_sign_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                             const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len,
+                             uint8_t* sig, int32_t* status, uint32_t max_iters, uint8_t* mu, uint32_t* iters,
+                             void* stream) {
   return mldsa_sign_call(ctx, alg, n, sk, msg, msg_off, rnd, ctx_str, ctx_len, sig, status, max_iters, true, mu, iters,
                          (hipStream_t)stream);
 }
 
-// Tests only (not in qrkem.h): qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed
-// c~' [n][64] (lambda / 4 bytes, then zeros), the w1Encode bytes [n][k 32 (6 or 4)] and a flag word
-// (bit 0: hint encoding malformed, bit 1: ||z||_inf >= gamma1 - beta, bit 2: c~ != c~'; bit 3, internal:
-// a row of 2^31 bytes or more).  A row with bit 0 or bit 3 set has zeros in the other three.  This is
-// what makes parity with tests/mldsa_spec.py byte-level instead of one boolean per row.
-extern "C" int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk,
-                                          const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
-                                          const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
-                                          uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream) {
+// test hook (qrkem_debug.h): qrk_sig_verify_batch for an ML-DSA name, with the trace outputs
+int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                               const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                               int32_t* status, uint8_t* mu, uint8_t* ctilde, uint8_t* w1, uint32_t* flags,
+                               void* stream) {
   if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
   const VerifyIo v{pk, msg, msg_off, sig, ctx_str, ctx_len, status};
   SigAlg a;
@@ -1563,13 +1541,11 @@ int qrk_mldsa_verify_keyed_batch(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_
                                  (hipStream_t)stream);
 }
 
-// Tests only (not in qrkem.h): qrk_mldsa_verify_keyed_batch with the trace outputs of qrk_dbg_mldsa_verify_trace; the
-// flag word has one more bit, 16: the row's key index is outside the set (zeros in the other three outputs).
-extern "C" int qrk_dbg_mldsa_verify_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n,
-                                                const uint32_t* key_index, const uint8_t* msg, const uint64_t* msg_off,
-                                                const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
-                                                int32_t* status, uint8_t* mu, uint8_t* ctilde, uint8_t* w1,
-                                                uint32_t* flags, void* stream) {
+// test hook (qrkem_debug.h): the call above with the trace outputs
+int qrk_dbg_mldsa_verify_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                     const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
+                                     const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
+                                     uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream) {
   if (n && (!mu || !ctilde || !w1 || !flags)) return fail("null trace buffer");
   return mldsa_verify_keyed_call(ctx, ks, n, key_index, msg, msg_off, sig, ctx_str, ctx_len, status,
                                  MldsaTrace{mu, ctilde, w1, flags}, (hipStream_t)stream);
@@ -1600,33 +1576,26 @@ int qrk_mldsa_sign_keyed_batch(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t 
                                MLDSA_SIGN_MAX_ITERS, false, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// Tests only (not in qrkem.h): qrk_mldsa_sign_keyed_batch with the loop's cap as an argument and the outputs of
-// qrk_dbg_mldsa_sign_trace: mu [n][64] (zeros for a refused row) and the iterations run, iters [n].
-extern "C" int qrk_dbg_mldsa_sign_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n,
-                                              const uint32_t* key_index, const uint8_t* msg, const uint64_t* msg_off,
-                                              const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig,
-                                              int32_t* status, uint32_t max_iters, uint8_t* mu, uint32_t* iters,
-                                              void* stream) {
+// test hook (qrkem_debug.h): the call above with the loop's cap as an argument and the trace outputs
+int qrk_dbg_mldsa_sign_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                   const uint8_t* msg, const uint64_t* msg_off, const uint8_t* rnd,
+                                   const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig, int32_t* status,
+                                   uint32_t max_iters, uint8_t* mu, uint32_t* iters, void* stream) {
   return mldsa_sign_keyed_call(ctx, ks, n, key_index, msg, msg_off, rnd, ctx_str, ctx_len, sig, status, max_iters, true,
                                mu, iters, (hipStream_t)stream);
 }
 
-// Tests and tools only (not in qrkem.h): which form of the keyed signing core later launches take (1: the NTT'd
-// secret vectors held in LDS, 2: read from the set; anything else: the default).  Returns the mode now set.
-extern "C" int qrk_dbg_mldsa_keyed_sign_mode(int mode) {
+// test and tool hook (qrkem_debug.h): which form of the keyed signing core later launches take
+int qrk_dbg_mldsa_keyed_sign_mode(int mode) {
   g_mldsa_keyed_sign_mode.store(mode == 1 || mode == 2 ? mode : MLDSA_KEYED_SIGN_DEFAULT, std::memory_order_relaxed);
   return g_mldsa_keyed_sign_mode.load(std::memory_order_relaxed);
 }
 
-// Tests only (not in qrkem.h): qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name that also writes, per row,
-// the H_msg digest [n][m], the FORS public key [n][n], the root every hypertree layer reconstructed
-// [n][d][n] and a flag word (bit 0: the top root differs from PK.root; bit 1, internal: a row of 2^31
-// bytes or more, whose other three outputs are zeros).  The production kernel stores them itself, in an
-// instantiation no other call launches; parity with tests/slhdsa_spec.py is byte-level per layer.
-extern "C" int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk,
-                                           const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
-                                           const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* digest,
-                                           uint8_t* fors_pk, uint8_t* roots, uint32_t* flags, void* stream) {
+// test hook (qrkem_debug.h): qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name, with the trace outputs
+int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                                const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                                int32_t* status, uint8_t* digest, uint8_t* fors_pk, uint8_t* roots, uint32_t* flags,
+                                void* stream) {
   if (n && (!digest || !fors_pk || !roots || !flags)) return fail("null trace buffer");
   const VerifyIo v{pk, msg, msg_off, sig, ctx_str, ctx_len, status};
   SigAlg a;
@@ -1634,13 +1603,9 @@ extern "C" int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t
   return slhdsa_verify_rows(ctx, a, n, v, SlhdsaTrace{digest, fors_pk, roots, flags}, (hipStream_t)stream);
 }
 
-// Tests only (not in qrkem.h): qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes, per
-// row, mu' = Decode(C - B'S) to mu_out [n][32] (len_mu = 16 / 24 / 32 bytes, then zeros).  The launches
-// are those of the public call; mu' is read from the scratch record k_fr_dec_m wrote (seeds[12..]) before
-// each chunk's cleanse.  On a ciphertext that fails the re-encryption check ss = H(ct || s) whatever
-// Decode returned, so this is the only place a wrong mu' on such a row shows.
-extern "C" int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
-                                          const uint8_t* sk, uint8_t* mu_out, void* stream) {
+// test hook (qrkem_debug.h): qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes mu'
+int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
+                               const uint8_t* sk, uint8_t* mu_out, void* stream) {
   if (!ctx) return fail("null context");
   const AlgInfo* a = resolve(alg);
   if (!a) return -1;

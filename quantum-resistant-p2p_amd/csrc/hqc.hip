@@ -26,6 +26,7 @@
 
 #include "keccak.cuh"
 #include "keccak_coop.cuh"
+#include "qrkem_debug.h"  // qrk_dbg_hqc_trace
 #include "qrkem_internal.h"
 
 namespace qrk {
@@ -1512,8 +1513,8 @@ hipError_t hqc_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct
 
 }  // namespace qrk
 
-#if QRK_HQC_TRACE
-extern "C" int qrk_dbg_hqc_trace(unsigned long long* out) {
+#if QRK_HQC_TRACE  // declared in qrkem_debug.h
+int qrk_dbg_hqc_trace(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(qrk::hqc::g_hqc_trace), sizeof(qrk::hqc::g_hqc_trace)) == hipSuccess ? 0 : -1;
 }
 #endif

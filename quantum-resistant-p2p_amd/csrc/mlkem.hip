@@ -48,6 +48,7 @@
 //   mlkem_arith.cuh   tables, fp32 modular arithmetic, NTTs, basemul
 #include "mlkem_layout.cuh"
 #include "mlkem_paths.h"
+#include "qrkem_debug.h"  // qrk_dbg_ss_trace (mlkem_one.cuh)
 
 #include "mlkem_batch.cuh"
 #include "mlkem_one.cuh"

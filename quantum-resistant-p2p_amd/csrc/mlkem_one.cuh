@@ -466,8 +466,8 @@ size_t mlkem_small_max() { return QRK_SMALL_MAX; }
 
 }  // namespace qrk
 
-#if QRK_SS_TRACE
-extern "C" int qrk_dbg_ss_trace(unsigned long long* out) {
+#if QRK_SS_TRACE  // declared in qrkem_debug.h, which mlkem.hip includes
+int qrk_dbg_ss_trace(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(qrk::mlkem::g_ss_trace), sizeof(qrk::mlkem::g_ss_trace)) == hipSuccess ? 0 : -1;
 }
 #endif

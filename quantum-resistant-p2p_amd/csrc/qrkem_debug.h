@@ -1,0 +1,123 @@
+// The library's test hooks: every exported qrk_dbg_* function that include/qrkem.h does not declare
+// (qrk_dbg_hqc_decaps_trace is the one it does).  Not part of the public ABI: tests and tools call them
+// through ctypes, and qrkem/_debug.py holds their one binding table, which tests/test_debug_abi.py
+// checks against this file parameter by parameter.  abi.cpp, mlkem.hip and hqc.hip include it, so a
+// definition that drifts from its declaration does not compile.  Keep the declarations plain: pointers,
+// size_t, int and uint32_t parameters, an int result (0, or -1 with qrk_last_error() set).
+#pragma once
+#include "../../include/qrkem.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// -DQRK_HOST_TRACE=1 builds only (abi.cpp): the steady-clock stamps, in ns, at the phases of the last
+// single-shot call, out[16] (tools/host_trace.py).
+#if QRK_HOST_TRACE
+int qrk_dbg_host_trace(long long* out);
+#endif
+
+// -DQRK_SS_TRACE=1 builds only (mlkem_one.cuh): the 100 MHz wall-clock phase marks of the last ML-KEM
+// single-shot kernel, g_ss_trace of mlkem_trace.cuh copied out whole (tools/single_shot_trace.py).
+#if QRK_SS_TRACE
+int qrk_dbg_ss_trace(unsigned long long* out);
+#endif
+
+// -DQRK_HQC_TRACE=1 builds only (hqc.hip): the phase marks workgroup QRK_HQC_TRACE_WG of k_hqc_enc_mul /
+// k_hqc_decode stamped, g_hqc_trace copied out whole (tools/hqc_trace.py).
+#if QRK_HQC_TRACE
+int qrk_dbg_hqc_trace(unsigned long long* out);
+#endif
+
+// The workgroup of role `role` of the pipelined single-shot ML-KEM KeyGen (PRF item N = role < 2K,
+// row r = role - 2K + 1) publishes its payload and flags 150 ms late, past every bounded wait
+// (-1: off).  Process-wide.
+int qrk_dbg_kg_late(int role);
+
+// Every ABI call (every chunk of a chunked one) fails as if its first launch had been rejected
+// (0: off): launch_begin() records hipErrorLaunchFailure.  The kernels themselves still launch, on
+// valid buffers, except where a launcher stops at the first failure.  Process-wide.
+int qrk_dbg_fail_launch(int on);
+
+// Batched ML-KEM Encaps / Decaps chunks of at most 2^15 handshakes fail right after the SampleNTT
+// fix-up counter parity flip, before their first launch (0: off), and the context's two fix-up
+// counter words and its parity read back (the re-zero path).
+int qrk_dbg_fail_after_flip(int on);
+int qrk_dbg_fixc_words(qrk_ctx* ctx, uint32_t* out, int* parity);
+
+// Nonzero words among the context's single-shot KeyGen flag / counter words, which must be zero
+// between calls (after a failed pipelined KeyGen too).
+int qrk_dbg_kg_flags_residue(qrk_ctx* ctx, uint64_t* out);
+
+// Nonzero bytes left in the ML-KEM per-handshake records of a chunk of n handshakes (mlkem_cleanse
+// wipes them after every chunk).
+int qrk_dbg_mlkem_records_residue(qrk_ctx* ctx, const char* alg, size_t n, uint64_t* out);
+
+// Poly1305 and GHASH on chosen keys.  Through the AEADs r, s and H are cipher outputs and cannot be
+// steered to their edge cases (r = 1 with an accumulator of exactly p + k, single-bit and all-ones H).
+// Device pointers; tag_i = Poly1305(key32_i = r | s, msg_i), msg ragged by msg_off [n+1];
+// out_i = GHASH_{h_i}(data_i), data_i a whole number of 16-byte blocks.
+int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off, uint8_t* tag,
+                           void* stream);
+int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
+                        void* stream);
+
+// qrk_mldsa_sign_batch with the loop's cap as an argument, which also writes, per row, mu [n][64] (zeros
+// for a row refused for its offsets or length) and the iterations run, iters [n] (0 for a refused row,
+// max_iters for one that exhausted them).  The production kernel stores them itself, in an instantiation
+// no other call launches; this is what pins the rejection loop against tests/mldsa_spec.py iteration by
+// iteration, and what lets a test reach the cap.
+int qrk_dbg_mldsa_sign_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* msg,
+                             const uint64_t* msg_off, const uint8_t* rnd, const uint8_t* ctx_str, size_t ctx_len,
+                             uint8_t* sig, int32_t* status, uint32_t max_iters, uint8_t* mu, uint32_t* iters,
+                             void* stream);
+
+// qrk_sig_verify_batch that also writes, per row, mu [n][64], the recomputed c~' [n][64] (lambda / 4
+// bytes, then zeros), the w1Encode bytes [n][k 32 (6 or 4)] and a flag word (bit 0: hint encoding
+// malformed, bit 1: ||z||_inf >= gamma1 - beta, bit 2: c~ != c~'; bit 3, internal: a row of 2^31 bytes
+// or more).  A row with bit 0 or bit 3 set has zeros in the other three.  This is what makes parity with
+// tests/mldsa_spec.py byte-level instead of one boolean per row.
+int qrk_dbg_mldsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                               const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                               int32_t* status, uint8_t* mu, uint8_t* ctilde, uint8_t* w1, uint32_t* flags,
+                               void* stream);
+
+// qrk_mldsa_verify_keyed_batch with the trace outputs of qrk_dbg_mldsa_verify_trace; the flag word has one
+// more bit, 16: the row's key index is outside the set (zeros in the other three outputs).
+int qrk_dbg_mldsa_verify_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                     const uint8_t* msg, const uint64_t* msg_off, const uint8_t* sig,
+                                     const uint8_t* ctx_str, size_t ctx_len, int32_t* status, uint8_t* mu,
+                                     uint8_t* ctilde, uint8_t* w1, uint32_t* flags, void* stream);
+
+// qrk_mldsa_sign_keyed_batch with the loop's cap as an argument and the outputs of qrk_dbg_mldsa_sign_trace:
+// mu [n][64] (zeros for a refused row) and the iterations run, iters [n].
+int qrk_dbg_mldsa_sign_keyed_trace(qrk_ctx* ctx, const qrk_mldsa_keyset* ks, size_t n, const uint32_t* key_index,
+                                   const uint8_t* msg, const uint64_t* msg_off, const uint8_t* rnd,
+                                   const uint8_t* ctx_str, size_t ctx_len, uint8_t* sig, int32_t* status,
+                                   uint32_t max_iters, uint8_t* mu, uint32_t* iters, void* stream);
+
+// Tests and tools: which form of the keyed signing core later launches take (1: the NTT'd secret vectors
+// held in LDS, 2: read from the set; anything else: the default).  Returns the mode now set.
+int qrk_dbg_mldsa_keyed_sign_mode(int mode);
+
+// qrk_sig_verify_batch for an SLH-DSA / SPHINCS+ name that also writes, per row, the H_msg digest [n][m],
+// the FORS public key [n][n], the root every hypertree layer reconstructed [n][d][n] and a flag word
+// (bit 0: the top root differs from PK.root; bit 1, internal: a row of 2^31 bytes or more, whose other
+// three outputs are zeros).  The production kernel stores them itself, in an instantiation no other call
+// launches; parity with tests/slhdsa_spec.py is byte-level per layer.
+int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* pk, const uint8_t* msg,
+                                const uint64_t* msg_off, const uint8_t* sig, const uint8_t* ctx_str, size_t ctx_len,
+                                int32_t* status, uint8_t* digest, uint8_t* fors_pk, uint8_t* roots, uint32_t* flags,
+                                void* stream);
+
+// qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes, per row, mu' = Decode(C - B'S) to
+// mu_out [n][32] (len_mu = 16 / 24 / 32 bytes, then zeros).  The launches are those of the public call;
+// mu' is read from the scratch record k_fr_dec_m wrote (seeds[12..]) before each chunk's cleanse.  On a
+// ciphertext that fails the re-encryption check ss = H(ct || s) whatever Decode returned, so this is the
+// only place a wrong mu' on such a row shows.
+int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
+                               const uint8_t* sk, uint8_t* mu_out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif

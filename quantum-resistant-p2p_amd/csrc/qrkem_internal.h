@@ -1,6 +1,7 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
 // launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
+// The exported test hooks (qrk_dbg_*) are declared in qrkem_debug.h and bound for ctypes in qrkem/_debug.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -14,19 +14,24 @@ ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "qrkem.h"
 
 
-def declared_functions():
-    text = HEADER.read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+def declared_functions(header=HEADER):
+    text = Path(header).read_text()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
     names = re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\(", text)
     skip = {"OQS_STATUS", "if", "sizeof", "extern", "keypair", "encaps", "decaps", "defined"}
     return sorted({n for n in names if (n.startswith("OQS_") or n.startswith("qrk_")) and n not in skip})
 
 
-def test_library_exports_every_declared_symbol():
+def exported_symbols():
+    """The names the loaded library defines in its dynamic symbol table."""
     import qrkem
     out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
                          check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_library_exports_every_declared_symbol():
+    exported = exported_symbols()
     missing = [n for n in declared_functions() if n not in exported]
     assert not missing, missing
     assert len(declared_functions()) >= 30

@@ -1,22 +1,18 @@
 """CPU: the AEAD entry points are exported, declared and bound, refuse unknown algorithm names, and the
 reference-shaped classes check their arguments before any GPU work."""
 import ctypes as ct
-import subprocess
 
 import pytest
 
-from test_abi import declared_functions
+from test_abi import declared_functions, exported_symbols
 
 AEAD_SYMBOLS = ("qrk_aead_seal_batch", "qrk_aead_open_batch")
 HOOKS = ("qrk_dbg_poly1305_batch", "qrk_dbg_ghash_batch")
 
 
 def test_aead_symbols_exported_declared_and_bound():
-    import qrkem
     from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     declared = declared_functions()
     for name in AEAD_SYMBOLS:
         assert name in exported and name in declared

@@ -141,19 +141,14 @@ def test_trace_hook_is_exported_undeclared_and_checks_its_arguments_first():
     """qrk_dbg_frodo_decaps_trace is a test hook: exported, kept out of the public header; a name that is
     no FrodoKEM parameter set, a null context and null buffers are refused before any device work."""
     import ctypes as ct
-    import subprocess
 
     import qrkem
-    from qrkem._native import LIB
-    from test_abi import declared_functions
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert "qrk_dbg_frodo_decaps_trace" in exported and "qrk_dbg_frodo_decaps_trace" not in declared_functions()
-    P = ct.c_void_p
-    fn = LIB.qrk_dbg_frodo_decaps_trace
-    fn.restype, fn.argtypes = ct.c_int, [P, ct.c_char_p, ct.c_size_t, P, P, P, P, P]
-    ctx = P(1)  # never dereferenced: the name and the buffers are checked first
+    from qrkem._debug import bind
+    from test_abi import declared_functions, exported_symbols
+    assert "qrk_dbg_frodo_decaps_trace" in exported_symbols()
+    assert "qrk_dbg_frodo_decaps_trace" not in declared_functions()
+    fn = bind().qrk_dbg_frodo_decaps_trace
+    ctx = ct.c_void_p(1)  # never dereferenced: the name and the buffers are checked first
     for alg, msg in ((b"ML-KEM-768", "not a FrodoKEM parameter set"), (b"HQC-128", "not a FrodoKEM parameter set"),
                      (b"FrodoKEM-640", "unsupported KEM")):
         assert fn(ctx, alg, 1, None, None, None, None, None) == -1

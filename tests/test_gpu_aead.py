@@ -136,9 +136,9 @@ def _packed(rows):
 
 def _hook(name, fixed, rows):
     """Run a qrk_dbg_* hook: `fixed` = n byte strings of equal length, `rows` ragged; 16-byte outputs."""
-    from qrkem._native import LIB, last_error
-    fn = getattr(LIB, name)
-    fn.restype, fn.argtypes = ct.c_int, [ct.c_size_t] + [ct.c_void_p] * 5
+    from qrkem._debug import bind
+    from qrkem._native import last_error
+    fn = getattr(bind(), name)
     n = len(rows)
     f = torch.from_numpy(np.frombuffer(b"".join(fixed), np.uint8).copy()).cuda()
     data, off = _packed(rows)

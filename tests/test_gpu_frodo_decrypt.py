@@ -16,7 +16,6 @@ Bar: byte-exact (integer work).  References: numpy int64 mod q for M, frodo_spec
 oracle.batch_decaps / batch_encaps for ss and ct (held to frodo_spec on these inputs in
 tests/test_frodo_edge_oracle.py).  No batch is larger than 1024 rows.
 """
-import ctypes as ct
 import hashlib
 import json
 from pathlib import Path
@@ -36,11 +35,7 @@ GOLD = json.loads((Path(__file__).parent / "golden" / "frodo_edge.json").read_te
 
 @pytest.fixture(scope="module")
 def engines():
-    from qrkem._native import LIB
     from qrkem.batch import BatchKEM
-    P = ct.c_void_p
-    LIB.qrk_dbg_frodo_decaps_trace.restype = ct.c_int
-    LIB.qrk_dbg_frodo_decaps_trace.argtypes = [P, ct.c_char_p, ct.c_size_t, P, P, P, P, P]
     return {a: BatchKEM(a, device=0) for a in ALL_ALGS}
 
 
@@ -55,7 +50,9 @@ def _host(t):
 
 def _trace(eng, sk, ct_):
     """(ss [n, ss_len], mu' [n, 32]) of qrk_dbg_frodo_decaps_trace; mu' is pre-filled so missing writes show."""
-    from qrkem._native import LIB, last_error
+    from qrkem._debug import bind
+    from qrkem._native import last_error
+    LIB = bind()
     n = sk.shape[0]
     assert n <= 1024
     sk_d, ct_d = _dev(sk), _dev(ct_)

@@ -34,12 +34,8 @@ FILL = 0xA5
 
 @pytest.fixture(scope="module")
 def lib():
-    from qrkem._native import LIB
-    LIB.qrk_dbg_fail_launch.restype, LIB.qrk_dbg_fail_launch.argtypes = ct.c_int, [ct.c_int]
-    for name in ("qrk_dbg_poly1305_batch", "qrk_dbg_ghash_batch"):
-        fn = getattr(LIB, name)
-        fn.restype, fn.argtypes = ct.c_int, [SZ, P, P, P, P, P]
-    return LIB
+    from qrkem._debug import bind
+    return bind()
 
 
 @pytest.fixture
@@ -294,8 +290,6 @@ def slh_sign(lib, ctx):
 def frodo_decaps_trace(lib, ctx):
     alg, n = "FrodoKEM-640-SHAKE", 64
     s, _, _, _, sk, c = _kem_chain(lib, ctx, alg, n)
-    lib.qrk_dbg_frodo_decaps_trace.restype = ct.c_int
-    lib.qrk_dbg_frodo_decaps_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P]
     ss, mu = _out(n, s["ss"]), _out(n, 32)
     return lambda: lib.qrk_dbg_frodo_decaps_trace(ctx, alg.encode(), n, ss.data_ptr(), c.data_ptr(), sk.data_ptr(),
                                                   mu.data_ptr(), _stream()), [ss, mu]

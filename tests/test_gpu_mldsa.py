@@ -25,11 +25,8 @@ def fixture():
 
 @pytest.fixture(scope="module")
 def lib():
-    from qrkem._native import LIB
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_mldsa_verify_trace.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_verify_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]
-    return LIB
+    from qrkem._debug import bind
+    return bind()
 
 
 @pytest.fixture(scope="module")

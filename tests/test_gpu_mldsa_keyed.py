@@ -88,16 +88,8 @@ def test_fixture_is_what_the_spec_says(keyed):
 # ------------------------------------------------------------------ the library
 @pytest.fixture(scope="module")
 def lib():
-    from qrkem._native import LIB
-    P, SZ = ct.c_void_p, ct.c_size_t
-    for fn, argtypes in (
-            ("qrk_dbg_mldsa_verify_trace", [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]),
-            ("qrk_dbg_mldsa_sign_trace", [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]),
-            ("qrk_dbg_mldsa_verify_keyed_trace", [P, P, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]),
-            ("qrk_dbg_mldsa_sign_keyed_trace", [P, P, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P])):
-        getattr(LIB, fn).restype = ct.c_int
-        getattr(LIB, fn).argtypes = argtypes
-    return LIB
+    from qrkem._debug import bind
+    return bind()
 
 
 @pytest.fixture(scope="module")
@@ -429,8 +421,6 @@ def test_sign_replays_the_golden_records(lib, ctx, golden_records, mode, name):
     set), each with status, mu, iteration counts and signatures equal to the per-row call's."""
     rows = golden_records[name]["rows"]
     sks = sorted({r["sk"] for r in rows})
-    lib.qrk_dbg_mldsa_keyed_sign_mode.restype = ct.c_int
-    lib.qrk_dbg_mldsa_keyed_sign_mode.argtypes = [ct.c_int]
     try:
         assert lib.qrk_dbg_mldsa_keyed_sign_mode(mode) == mode
         with KeySet(lib, ctx, name, sks, True) as ks:

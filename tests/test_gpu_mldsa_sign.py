@@ -34,11 +34,8 @@ def keys(sets):
 
 @pytest.fixture(scope="module")
 def lib():
-    from qrkem._native import LIB
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_mldsa_sign_trace.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_sign_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]
-    return LIB
+    from qrkem._debug import bind
+    return bind()
 
 
 @pytest.fixture(scope="module")

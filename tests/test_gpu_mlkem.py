@@ -378,9 +378,10 @@ def test_keygen_pipe_forced_timeout(engines, alg, item):
     import ctypes as ct
     import oracle as orc
     from qrkem import oqs
-    from qrkem._native import LIB, last_error
+    from qrkem._debug import bind
+    from qrkem._native import last_error
+    LIB = bind()
     dbg = LIB.qrk_dbg_kg_late
-    dbg.argtypes, dbg.restype = [ct.c_int], ct.c_int
     rng = np.random.default_rng(item + 31 * len(alg))
     kc, kc_lost = (rng.integers(0, 256, 64, dtype=np.uint8).tobytes() for _ in range(2))
     kcb, kcb_lost = (rng.integers(0, 256, (3, 64), dtype=np.uint8) for _ in range(2))
@@ -395,10 +396,8 @@ def test_keygen_pipe_forced_timeout(engines, alg, item):
             eng.keypair(coins=kcb_lost)
         assert "hand-off timeout" in last_error()
         # the straggler set its flags after the collector's reset; the failed call re-zeroed them
-        res = LIB.qrk_dbg_kg_flags_residue
-        res.argtypes, res.restype = [ct.c_void_p, ct.POINTER(ct.c_uint64)], ct.c_int
         cnt = ct.c_uint64(1)
-        assert res(eng._ctx, ct.byref(cnt)) == 0 and cnt.value == 0
+        assert LIB.qrk_dbg_kg_flags_residue(eng._ctx, ct.byref(cnt)) == 0 and cnt.value == 0
     finally:
         dbg(-1)
     opk, osk = orc.keypair(alg, kc)
@@ -420,8 +419,9 @@ def test_fixup_counters_rezeroed_after_failed_chunk(op):
     word would carry the previous call's count as well."""
     import ctypes as ct
     import oracle as orc
-    from qrkem._native import LIB
+    from qrkem._debug import bind
     from qrkem.batch import BatchKEM
+    LIB = bind()
     alg, k = "ML-KEM-768", 3
     rng = np.random.default_rng(1234)
     for _ in range(4000):
@@ -435,10 +435,7 @@ def test_fixup_counters_rezeroed_after_failed_chunk(op):
     opk, osk = orc.batch_keypair(alg, kc0)
     opk[:, -32:] = np.frombuffer(rho, dtype=np.uint8)
     osk[:, 768 * k:768 * k + 32] = np.frombuffer(rho, dtype=np.uint8)
-    fail = LIB.qrk_dbg_fail_after_flip
-    fail.argtypes, fail.restype = [ct.c_int], ct.c_int
-    words = LIB.qrk_dbg_fixc_words
-    words.argtypes, words.restype = [ct.c_void_p, ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_int)], ct.c_int
+    fail, words = LIB.qrk_dbg_fail_after_flip, LIB.qrk_dbg_fixc_words
     eng = BatchKEM(alg, device=0)
 
     def run(n, seed):
@@ -480,13 +477,11 @@ def test_context_state_interleaved_keygen_and_direct_rho():
     zero after every step; after the last, parity 0 and the counter the next call counts into zero."""
     import ctypes as ct
     import oracle as orc
-    from qrkem._native import LIB
+    from qrkem._debug import bind
     from qrkem.batch import BatchKEM
+    LIB = bind()
     alg, n_kg, n = "ML-KEM-512", 16, 1088
-    res = LIB.qrk_dbg_kg_flags_residue
-    res.argtypes, res.restype = [ct.c_void_p, ct.POINTER(ct.c_uint64)], ct.c_int
-    words = LIB.qrk_dbg_fixc_words
-    words.argtypes, words.restype = [ct.c_void_p, ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_int)], ct.c_int
+    res, words = LIB.qrk_dbg_kg_flags_residue, LIB.qrk_dbg_fixc_words
     eng = BatchKEM(alg, device=0)
 
     def flags_clear():

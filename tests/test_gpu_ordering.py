@@ -169,12 +169,11 @@ def test_mlkem_records_wiped(alg):
     """The batched ML-KEM path leaves no per-handshake key material (r / sigma, m', K', Kbar) in
     scratch once a call has completed (mlkem_cleanse after every chunk, stream-ordered)."""
     import ctypes as ct
-    from qrkem._native import LIB
+    from qrkem._debug import bind
     from qrkem.batch import BatchKEM
     n = 5000  # batched (above the one-launch sizes), ragged
     eng = BatchKEM(alg, device=0)
-    fn = LIB.qrk_dbg_mlkem_records_residue
-    fn.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_size_t, ct.POINTER(ct.c_uint64)]
+    fn = bind().qrk_dbg_mlkem_records_residue
     out = ct.c_uint64()
 
     def residue():

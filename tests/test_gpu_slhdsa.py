@@ -59,11 +59,8 @@ def signed(fixture):
 
 @pytest.fixture(scope="module")
 def lib():
-    from qrkem._native import LIB
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_slhdsa_verify_trace.restype = ct.c_int
-    LIB.qrk_dbg_slhdsa_verify_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]
-    return LIB
+    from qrkem._debug import bind
+    return bind()
 
 
 @pytest.fixture(scope="module")

@@ -2,21 +2,17 @@
 refuse bad names and over-long context strings before any device work, leave the OQS_SIG registry
 empty, and the reference-shaped class checks its arguments without a GPU."""
 import ctypes as ct
-import subprocess
 
 import pytest
 
-from test_abi import declared_functions
+from test_abi import declared_functions, exported_symbols
 
 SIZES = {"ML-DSA-44": (1312, 2560, 2420), "ML-DSA-65": (1952, 4032, 3309), "ML-DSA-87": (2592, 4896, 4627)}
 
 
 def test_sig_symbols_exported_declared_and_bound():
-    import qrkem
     from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     declared = declared_functions()
     for name, nargs in (("qrk_sig_sizes", 2), ("qrk_sig_verify_batch", 11)):
         assert name in exported and name in declared

@@ -4,11 +4,10 @@ MLDSAKeySet and the keyed methods have the stated surface, raise ValueError on a
 and need a device for everything else."""
 import ctypes as ct
 import inspect
-import subprocess
 
 import pytest
 
-from test_abi import HEADER, declared_functions
+from test_abi import HEADER, declared_functions, exported_symbols
 
 NAMES = ("ML-DSA-44", "ML-DSA-65", "ML-DSA-87")
 CTX = ct.c_void_p(1)  # never dereferenced: every check below comes before the context is used
@@ -37,11 +36,8 @@ def sign(ctx, ks, n, ctx_len=0, bufs=None, ctx_str=None, index=None):
 
 
 def test_symbols_are_exported_declared_and_bound():
-    import qrkem
     from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     declared = declared_functions()
     for name, nargs in PUBLIC.items():
         assert name in exported and name in declared and len(getattr(LIB, name).argtypes) == nargs, name
@@ -87,12 +83,9 @@ def test_keyed_calls_check_order_and_messages():
 
 def test_trace_hooks_check_like_the_calls():
     import qrkem
-    from qrkem._native import LIB
-    P, SZ = ct.c_void_p, ct.c_size_t
+    from qrkem._debug import bind
+    LIB = bind()
     v, s = LIB.qrk_dbg_mldsa_verify_keyed_trace, LIB.qrk_dbg_mldsa_sign_keyed_trace
-    v.restype = s.restype = ct.c_int
-    v.argtypes = [P, P, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]
-    s.argtypes = [P, P, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]
     assert v(None, None, 0, None, None, None, None, None, 0, None, None, None, None, None, None) == -1
     assert "null context" in qrkem.last_error()
     assert v(CTX, None, 0, None, None, None, None, None, 0, None, None, None, None, None, None) == -1

@@ -2,11 +2,10 @@
 in the documented order before any device work, refuse hash-based names by name; MLDSASigner has the reference's
 surface and needs a device for every signing call, while MLDSASignature stays verification-only."""
 import ctypes as ct
-import subprocess
 
 import pytest
 
-from test_abi import declared_functions
+from test_abi import declared_functions, exported_symbols
 
 NAMES = ("ML-DSA-44", "ML-DSA-65", "ML-DSA-87")
 SIZES = {2: (1312, 2560, 2420), 3: (1952, 4032, 3309), 5: (2592, 4896, 4627)}
@@ -25,11 +24,8 @@ def sign(ctx, alg, n, ctx_len=0, bufs=None, ctx_str=None):
 
 
 def test_symbols_are_exported_declared_and_bound():
-    import qrkem
     from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     declared = declared_functions()
     for name, nargs in (("qrk_mldsa_keypair_batch", 7), ("qrk_mldsa_sign_batch", 12)):
         assert name in exported and name in declared and len(getattr(LIB, name).argtypes) == nargs
@@ -64,11 +60,9 @@ def test_check_order_and_messages():
 
 
 def test_trace_hook_checks_like_the_call():
-    from qrkem._native import LIB
     import qrkem
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_mldsa_sign_trace.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_sign_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]
+    from qrkem._debug import bind
+    LIB = bind()
     none = [None] * 5
     assert LIB.qrk_dbg_mldsa_sign_trace(None, b"ML-DSA-65", 0, *none, 0, None, None, 814, None, None, None) == -1
     assert "null context" in qrkem.last_error()

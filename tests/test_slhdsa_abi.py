@@ -2,11 +2,10 @@
 context-string misuses before any device work, keep the OQS_SIG registry empty, export the test hook
 without declaring it, and SPHINCSSignature checks its arguments without a GPU."""
 import ctypes as ct
-import subprocess
 
 import pytest
 
-from test_abi import declared_functions
+from test_abi import declared_functions, exported_symbols
 
 SIZES = {"128f": (32, 64, 17088), "192f": (48, 96, 35664), "256f": (64, 128, 49856)}
 NAMES = {f(s): SIZES[s] for s in SIZES for f in (lambda s: f"SPHINCS+-SHA2-{s}-simple", lambda s: f"SLH-DSA-SHA2-{s}")}
@@ -49,18 +48,14 @@ def test_context_rules_are_checked_before_any_device_work():
 
 def test_trace_hook_is_exported_and_not_declared():
     import qrkem
-    from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    from qrkem._debug import bind
+    LIB = bind()
+    exported = exported_symbols()
     declared = declared_functions()
     assert "qrk_dbg_slhdsa_verify_trace" in exported and "qrk_dbg_slhdsa_verify_trace" not in declared
     for name, nargs in (("qrk_sig_sizes", 2), ("qrk_sig_verify_batch", 11)):
         assert name in exported and name in declared and len(getattr(LIB, name).argtypes) == nargs
     # each family's hook refuses the other family's names
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_slhdsa_verify_trace.restype = ct.c_int
-    LIB.qrk_dbg_slhdsa_verify_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]
     args = [None, None, None, None, None, 0, None, None, None, None, None, None]
     assert LIB.qrk_dbg_slhdsa_verify_trace(ct.c_void_p(1), b"ML-DSA-65", 0, *args) == -1
     assert "unsupported signature algorithm" in qrkem.last_error()

@@ -2,11 +2,10 @@
 documented order before any device work, refuse ML-DSA names by name; SPHINCSSignature keeps raising
 NotImplementedError by default and, with signing=True, needs a device for every signing call."""
 import ctypes as ct
-import subprocess
 
 import pytest
 
-from test_abi import declared_functions
+from test_abi import declared_functions, exported_symbols
 
 SETS = ("128f", "192f", "256f")
 NAMES = [f"SPHINCS+-SHA2-{s}-simple" for s in SETS] + [f"SLH-DSA-SHA2-{s}" for s in SETS]
@@ -24,11 +23,8 @@ def sign(ctx, alg, n, ctx_len=0):
 
 
 def test_symbols_are_exported_and_declared():
-    import qrkem
     from qrkem._native import LIB
-    out = subprocess.run(["nm", "-D", "--defined-only", str(qrkem.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     declared = declared_functions()
     for name, nargs in (("qrk_sig_keypair_batch", 7), ("qrk_sig_sign_batch", 12)):
         assert name in exported and name in declared and len(getattr(LIB, name).argtypes) == nargs

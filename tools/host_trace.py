@@ -15,10 +15,9 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "quantum-resistant-p2p_amd"))
 from qrkem import oqs  # noqa: E402
-from qrkem._native import LIB  # noqa: E402
+from qrkem._debug import bind  # noqa: E402
 
-fn = LIB.qrk_dbg_host_trace
-fn.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
+fn = bind().qrk_dbg_host_trace
 ALG, N = sys.argv[1] if len(sys.argv) > 1 else "ML-KEM-768", 300
 kem = oqs.KeyEncapsulation(ALG)
 pk = kem.generate_keypair()

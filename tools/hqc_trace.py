@@ -12,13 +12,12 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "quantum-resistant-p2p_amd"))
 import torch  # noqa: E402
-from qrkem._native import LIB  # noqa: E402
+from qrkem._debug import bind  # noqa: E402
 from qrkem.batch import BatchKEM  # noqa: E402
 
 ALG = sys.argv[1] if len(sys.argv) > 1 else "HQC-128"
 N, R = 1 << 16, 7
-fn = LIB.qrk_dbg_hqc_trace
-fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
+fn = bind().qrk_dbg_hqc_trace
 ENC = {1: "A: h, s doubled, supports, GF tables", 24: "B: start", 25: "B: dedupe r1 (wave 0)",
        26: "B: RS parity (wave 3)", 2: "B: barrier", 3: "C: sparse_dense (own)",
        4: "C: barrier (all classes)", 5: "prod_combine", 6: "message assembly", 7: "stores"}

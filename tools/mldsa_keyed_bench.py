@@ -35,8 +35,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import qrkem  # noqa: E402
-from qrkem._native import LIB  # noqa: E402
+from qrkem._debug import bind  # noqa: E402
 
+LIB = bind()
 LEVEL = {"ML-DSA-44": 2, "ML-DSA-65": 3, "ML-DSA-87": 5}
 VERIFY_MSG_BYTES, SIGN_MSG_BYTES = 2500, 64
 SIGN_MODES = {"keyed_lds": 1, "keyed_l2": 2}
@@ -148,9 +149,6 @@ def bench_verify(a, name: str, s, rng) -> None:
 
 
 def iterations(s, sk, ms, off, n: int) -> float:
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_mldsa_sign_trace.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_sign_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]
     sig = torch.empty((n, s.signature_size), dtype=torch.uint8, device="cuda")
     status = torch.empty((n,), dtype=torch.int32, device="cuda")
     mu = torch.empty((n, 64), dtype=torch.uint8, device="cuda")
@@ -164,8 +162,6 @@ def iterations(s, sk, ms, off, n: int) -> float:
 
 
 def bench_sign(a, name: str, s, rng) -> None:
-    LIB.qrk_dbg_mldsa_keyed_sign_mode.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_keyed_sign_mode.argtypes = [ct.c_int]
     default_mode = LIB.qrk_dbg_mldsa_keyed_sign_mode(0)
     rows = [int(x) for x in a.sign_rows.split(",")]
     _, sk1 = s.generate_keypair_batch(1, seeds=rng.integers(0, 256, size=(1, 32), dtype=np.uint8))

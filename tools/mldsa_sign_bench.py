@@ -36,8 +36,9 @@ import torch  # noqa: E402
 import make_golden_mldsa_sign as gold  # noqa: E402
 import mldsa_spec as spec  # noqa: E402
 import qrkem  # noqa: E402
-from qrkem._native import LIB  # noqa: E402
+from qrkem._debug import bind  # noqa: E402
 
+LIB = bind()
 LEVEL = {"ML-DSA-44": 2, "ML-DSA-65": 3, "ML-DSA-87": 5}
 MSG_BYTES = 64
 
@@ -73,9 +74,6 @@ def timed(steps: int, call) -> list:
 
 def iterations(s, sk, ms, off, n: int):
     """(mean, max) of the iterations the rows of this batch run: one traced call."""
-    P, SZ = ct.c_void_p, ct.c_size_t
-    LIB.qrk_dbg_mldsa_sign_trace.restype = ct.c_int
-    LIB.qrk_dbg_mldsa_sign_trace.argtypes = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, ct.c_uint32, P, P, P]
     sig = torch.empty((n, s.signature_size), dtype=torch.uint8, device="cuda")
     status = torch.empty((n,), dtype=torch.int32, device="cuda")
     mu = torch.empty((n, 64), dtype=torch.uint8, device="cuda")

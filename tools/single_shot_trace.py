@@ -12,12 +12,11 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "quantum-resistant-p2p_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from qrkem._native import LIB  # noqa: E402
+from qrkem._debug import bind  # noqa: E402
 from qrkem.batch import BatchKEM  # noqa: E402
 
 ALG, N = sys.argv[1] if len(sys.argv) > 1 else "ML-KEM-768", 100
-fn = LIB.qrk_dbg_ss_trace
-fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
+fn = bind().qrk_dbg_ss_trace
 MARKS = {
     # k_keygen_multi (n = 1): one workgroup per PRF / SampleNTT item, the last to count in finishes
     # k_keygen_pipe (n = 1 host-pointer calls, the default there): t = 0 is the collector workgroup's start
