@@ -270,6 +270,74 @@ int qrk_aead_open_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *
                         const uint64_t *sealed_off, const uint8_t *aad, const uint64_t *aad_off, size_t aad_len,
                         uint8_t *pt, int32_t *status, void *stream);
 
+/* The same two operations for long rows: one row is sealed or opened by many workgroups instead of one
+ * lane (a file sent whole, messaging.py:1707-1713).  The bytes written are those of qrk_aead_seal_batch /
+ * qrk_aead_open_batch, and so are the arguments, the row layout, NULL nonces, the o < 28 i rule of Open,
+ * n == 0 and stream ordering.  max_len is the caller's bound on any row's plaintext length (it sizes the
+ * grid and the scratch): 0, or 2^31 and more, returns -1; a row longer than max_len is treated like a row
+ * with a bad aad span: Seal leaves it unwritten, Open gives it status -1 and writes nothing for it.
+ * Argument checks, in order: ctx, alg, n == 0 (returns 0), NULL buffers, aad_len, max_len, then the grid
+ * (n ceil(max_len / S) workgroups must stay below 2^31) and the scratch budget below; each failure
+ * returns -1 with qrk_last_error() set before any device work.
+ *
+ * qrk_aead_long_layout (host only) gives out = { S, C, the tail's fan-in, scratch bytes per segment }:
+ * a row is cut into segments of S = 256 C bytes, one 256-lane workgroup each, a lane owning C consecutive
+ * bytes (S = 65536, C = 256).  Segments are counted from the END of the row, so a row's short segment is
+ * its first one.  Each segment leaves a partial MAC (16 bytes of GHASH, or five Poly1305 limbs in 32
+ * bytes) in the context's scratch and one 64-lane workgroup per row combines them as a tree over powers
+ * of H^(S/16) / r^(S/16), finishes the tag and, on Open, compares it without early exit; a second pass
+ * then decrypts the rows that verified and writes zeros over the plaintext span of those that did not, so
+ * no plaintext byte of an unauthenticated row is ever written.  Associated data is absorbed serially (it
+ * is a message id in the reference); keep it short.
+ * Scratch: per row ceil(max_len / S) partials plus one 4-byte verdict word, i.e.
+ * n (ceil(max_len / S) out[3] + 4) bytes; beyond the context's scratch budget (48 GiB unless the library
+ * was built with another QRK_SCRATCH_GIB) the call returns -1.  The partials are secret-derived (H or r
+ * can be solved from one of them and the public ciphertext): they exist only in that scratch, the
+ * combining workgroup overwrites its row's whole partial span with zeros once it has consumed it (a
+ * call whose launch failed wipes the span itself), and qrk_ctx_cleanse covers them like the rest of the
+ * scratch.  No round key, H, r or s reaches global memory or a kernel argument.
+ *
+ * When to use which (measured on one MI355X, n = 1, tools/aead_long_bench.py, medians in ms; "-": the
+ * one-lane call takes more than a second there and is not timed):
+ *      bytes   GCM seal lane/long   GCM open lane/long   ChaCha seal lane/long   ChaCha open lane/long
+ *      4 KiB      2.17 / 0.34          2.20 / 0.35           0.71 / 0.053            0.72 / 0.058
+ *     16 KiB      8.95 / 0.34          9.20 / 0.34           2.80 / 0.051            2.81 / 0.056
+ *     64 KiB      35.5 / 0.34          35.3 / 0.35           11.1 / 0.052            11.1 / 0.058
+ *    256 KiB     137.6 / 0.34         138.0 / 0.35           43.9 / 0.053            44.1 / 0.059
+ *      1 MiB     572.8 / 0.44         571.3 / 0.41          178.5 / 0.060           180.1 / 0.064
+ *      4 MiB         - / 0.34             - / 0.35          702.2 / 0.089           738.5 / 0.145
+ *     16 MiB         - / 0.38             - / 0.38              - / 0.072               - / 0.071
+ *     64 MiB         - / 0.85             - / 0.83              - / 0.18                - / 0.20
+ * 64 rows of 4 KiB: GCM 2.46 / 0.35 (seal), ChaCha20-Poly1305 1.12 / 0.055: the long pair wins there too.
+ * qrkem.symmetric routes a call to the long pair when the longest row is known to the host and is at
+ * least long_min_bytes = 4096, the smallest size measured: the long pair was faster at every measured size
+ * (a one-lane GCM call costs about 0.55 ms per KiB; the long calls start at 0.34 ms, most of it the 64 KiB AES
+ * table filled by the 64 lanes of the combining workgroup).  Batches of more than 64 rows, the largest
+ * batch measured, stay on the one-lane pair (long_max_rows). */
+int qrk_aead_long_layout(const char *alg, size_t out[4]);
+int qrk_aead_seal_long_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *nonces,
+                             const uint8_t *pt, const uint64_t *pt_off, const uint8_t *aad,
+                             const uint64_t *aad_off, size_t aad_len, size_t max_len, uint8_t *sealed,
+                             void *stream);
+int qrk_aead_open_long_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *sealed,
+                             const uint64_t *sealed_off, const uint8_t *aad, const uint64_t *aad_off,
+                             size_t aad_len, size_t max_len, uint8_t *pt, int32_t *status, void *stream);
+/* TEST HOOKS, not for applications (declared here beside qrk_dbg_hqc_decaps_trace: the hook header
+ * csrc/qrkem_debug.h and its binding table are pinned at their present entries by tests/test_debug_abi.py).
+ * The segment and tail kernels' MAC machinery of the long calls as a bare MAC under a caller-chosen
+ * H (h [n][16]) or Poly1305 key32 = r | s ([n][32]), as qrk_dbg_ghash_batch / qrk_dbg_poly1305_batch of
+ * csrc/qrkem_debug.h: device pointers, rows ragged by n + 1 offsets, whole 16-byte blocks (a trailing
+ * partial block is ignored), rows above max_len left unwritten; out / tag [n][16].  Through the AEADs
+ * H, r and s are cipher outputs and cannot be steered to their edge cases, and the block counts at which
+ * a wrong power of the multiplier would show cannot be met with a chosen multiplier.
+ * qrk_dbg_aead_long_residue: out[0] = the OR of every byte of the segment-partial region the context's
+ * last long call (or hook) used; 0 after any completed call. */
+int qrk_dbg_ghash_long_batch(qrk_ctx *ctx, size_t n, const uint8_t *h, const uint8_t *data, const uint64_t *data_off,
+                             size_t max_len, uint8_t *out, void *stream);
+int qrk_dbg_poly1305_long_batch(qrk_ctx *ctx, size_t n, const uint8_t *key32, const uint8_t *msg,
+                                const uint64_t *msg_off, size_t max_len, uint8_t *tag, void *stream);
+int qrk_dbg_aead_long_residue(qrk_ctx *ctx, uint64_t *out);
+
 /* ML-DSA signature verification (FIPS 204 final, "pure" ML-DSA: Verify, Algorithm 3), the step the
  * reference runs on every handshake and chat message (signatures.py:167 from messaging.py:721, 933,
  * 1174, 1480).  alg: "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; any other name returns -1 with

@@ -1,5 +1,5 @@
 // The library's test hooks: every exported qrk_dbg_* function that include/qrkem.h does not declare
-// (qrk_dbg_hqc_decaps_trace is the one it does).  Not part of the public ABI: tests and tools call them
+// (it declares qrk_dbg_hqc_decaps_trace and the three hooks of the long AEAD calls).  Not part of the public ABI: tests and tools call them
 // through ctypes, and qrkem/_debug.py holds their one binding table, which tests/test_debug_abi.py
 // checks against this file parameter by parameter.  abi.cpp, mlkem.hip and hqc.hip include it, so a
 // definition that drifts from its declaration does not compile.  Keep the declarations plain: pointers,

@@ -1,5 +1,5 @@
 // Internal host-side interface between the C-ABI (abi.cpp) and the kernel
-// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip,
+// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 // The exported test hooks (qrk_dbg_*) are declared in qrkem_debug.h and bound for ctypes in qrkem/_debug.py.
 #pragma once
@@ -250,6 +250,29 @@ hipError_t dbg_poly1305(size_t n, const uint8_t* key32, const uint8_t* msg, cons
                         hipStream_t st);
 hipError_t dbg_ghash(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                      hipStream_t st);
+
+// AEAD with one row spread over many workgroups (aead_long.hip): the contracts of aead_seal / aead_open, rows of
+// at most max_len plaintext bytes (0 < max_len < 2^31; a longer row is refused like a row with a bad span).
+// aead_long_layout: { segment bytes S, bytes per lane C, tail fan-in, scratch bytes per segment partial }.
+// scratch: aead_long_scratch_bytes, of which the first aead_long_part_bytes hold the segment partials (secret-
+// derived; zero again when the call's kernels have run, or wiped by the launcher if a launch failed) and the
+// rest one verdict word per row.  The grid is aead_long_workgroups(n, max_len), which must be below 2^31.
+void aead_long_layout(AeadAlg alg, size_t out[4]);
+size_t aead_long_part_bytes(AeadAlg alg, size_t n, size_t max_len);
+size_t aead_long_scratch_bytes(AeadAlg alg, size_t n, size_t max_len);
+size_t aead_long_workgroups(size_t n, size_t max_len);
+hipError_t aead_seal_long(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* nonces, const uint8_t* pt,
+                          const uint64_t* pt_off, const uint8_t* aad, const uint64_t* aad_off, size_t aad_len,
+                          size_t max_len, uint8_t* sealed, void* scratch, hipStream_t st);
+hipError_t aead_open_long(AeadAlg alg, size_t n, const uint8_t* keys, const uint8_t* sealed, const uint64_t* sealed_off,
+                          const uint8_t* aad, const uint64_t* aad_off, size_t aad_len, size_t max_len, uint8_t* pt,
+                          int32_t* status, void* scratch, hipStream_t st);
+// tests only: the same segment and tail machinery as a bare MAC under a chosen H ([n][16]) or key32 = r | s
+// ([n][32]) over whole 16-byte blocks; scratch as the GCM / ChaCha20-Poly1305 call of the same n and max_len
+hipError_t dbg_ghash_long(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, size_t max_len,
+                          uint8_t* out, void* scratch, hipStream_t st);
+hipError_t dbg_poly1305_long(size_t n, const uint8_t* key32, const uint8_t* msg, const uint64_t* msg_off, size_t max_len,
+                             uint8_t* tag, void* scratch, hipStream_t st);
 
 // A signature launcher's parameter-set index as a compile-time constant: f(std::integral_constant<int, W>{}) for
 // the W < N that equals `which`, hipErrorInvalidValue for any other value.

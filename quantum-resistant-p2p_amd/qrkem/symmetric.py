@@ -5,7 +5,10 @@
 ``encrypt(key, plaintext, associated_data=None)`` returning nonce (12) || ciphertext || tag (16) and
 ``decrypt(key, ciphertext, associated_data=None)``, with the same ``ValueError``s.  The single calls are
 n = 1 batches of ``qrk_aead_seal_batch`` / ``qrk_aead_open_batch`` (aead.hip); like ``_native.py`` there
-is no CPU fallback.  Each class adds ``encrypt_batch`` / ``decrypt_batch`` over n keys at once.
+is no CPU fallback.  Each class adds ``encrypt_batch`` / ``decrypt_batch`` over n keys at once.  Where the
+host knows the longest row and it reaches ``long_min_bytes``, the same calls go through
+``qrk_aead_seal_long_batch`` / ``qrk_aead_open_long_batch`` (aead_long.hip: one row across many workgroups)
+and return the same bytes.
 
 Ragged batches travel as :class:`PackedRows` (concatenated bytes plus n + 1 offsets on the device), the
 packing :func:`qrkem.handshake.pack_infos` / :class:`qrkem.handshake.PackedInfos` use for HKDF infos.
@@ -125,6 +128,60 @@ def open_rows(ctx, alg: str, device: int, keys, sealed: PackedRows, aad: Optiona
     return sealed.shifted(-OVERHEAD, out), status
 
 
+def seal_rows_long(ctx, alg: str, device: int, keys, rows: PackedRows, aad: Optional[PackedInfos], nonces,
+                   max_len: int) -> PackedRows:
+    """:func:`seal_rows` through qrk_aead_seal_long_batch.  ``max_len`` (1 .. 2^31 - 1): the caller's bound on
+    any row's plaintext length; a longer row is left unwritten."""
+    n = rows.n
+    _check_dev(keys, 32, "AEAD keys", n)
+    if nonces is not None:
+        _check_dev(nonces, NONCE_LEN, "AEAD nonces", n)
+    out = torch.empty((max(rows.total + OVERHEAD * n, 1),), dtype=torch.uint8, device=rows.data.device)
+    rc = LIB.qrk_aead_seal_long_batch(ctx, alg.encode(), n, _ptr(keys), _ptr(nonces), _ptr(rows.data),
+                                      _ptr(rows.off), _ptr(aad.data) if aad else None,
+                                      _ptr(aad.off) if aad else None, aad.length if aad else 0, max_len,
+                                      _ptr(out), _stream(device))
+    if rc != 0:
+        raise RuntimeError(f"qrkem AEAD seal failed ({alg}): {last_error()}")
+    return rows.shifted(OVERHEAD, out)
+
+
+def open_rows_long(ctx, alg: str, device: int, keys, sealed: PackedRows, aad: Optional[PackedInfos], max_len: int):
+    """:func:`open_rows` through qrk_aead_open_long_batch.  ``max_len``: the bound on any row's plaintext
+    length (its sealed length less 28); a longer row gets status -1 and nothing is written for it."""
+    n = sealed.n
+    _check_dev(keys, 32, "AEAD keys", n)
+    if sealed.total < OVERHEAD * n:
+        raise ValueError(f"{n} sealed rows need at least {OVERHEAD * n} bytes, got {sealed.total}")
+    out = torch.empty((max(sealed.total - OVERHEAD, 1),), dtype=torch.uint8, device=sealed.data.device)
+    status = torch.empty((n,), dtype=torch.int32, device=sealed.data.device)
+    rc = LIB.qrk_aead_open_long_batch(ctx, alg.encode(), n, _ptr(keys), _ptr(sealed.data), _ptr(sealed.off),
+                                      _ptr(aad.data) if aad else None, _ptr(aad.off) if aad else None,
+                                      aad.length if aad else 0, max_len, _ptr(out), _ptr(status), _stream(device))
+    if rc != 0:
+        raise RuntimeError(f"qrkem AEAD open failed ({alg}): {last_error()}")
+    return sealed.shifted(-OVERHEAD, out), status
+
+
+# The longest row from which the long calls are faster than the one-lane calls for Seal and for Open, both
+# AEADs, at every larger measured size, rounded up to a power of two (tools/aead_long_bench.py on one MI355X,
+# profiles/aead_long/bench.jsonl; DESIGN.md section 4 has the table).
+LONG_MIN_BYTES = 1 << 12
+# ... in batches of at most this many rows, the largest batch measured (the long calls won there too).  Above it
+# every row keeps its own lane: nothing was measured there.
+LONG_MAX_ROWS = 64
+
+
+def _longest(rows, overhead: int = 0) -> Optional[int]:
+    """The longest row's payload length where the host knows it without a device read: a list of byte
+    strings or an [n, L] tensor; None for PackedRows (its caller passes ``max_len=``)."""
+    if isinstance(rows, PackedRows):
+        return None
+    if _is_dev(rows):
+        return max(int(rows.shape[1]) - overhead, 0) if rows.dim() == 2 else None
+    return max((len(x) - overhead for x in rows), default=0)
+
+
 def _rows_in(rows, device: int):
     """(PackedRows, kind) of a list of byte strings, an [n, L] device tensor or PackedRows."""
     if isinstance(rows, PackedRows):
@@ -168,10 +225,23 @@ class _GpuAEAD(SymmetricAlgorithm):
     object (as the reference does at start-up, messaging.py:127) needs no GPU; using it does."""
 
     _ALG = ""
+    #: rows at least this long (known to the host: a list, an [n, L] tensor, or ``max_len=`` beside
+    #: PackedRows) go through the long calls; None: never, 0: always.  Same bytes either way.
+    long_min_bytes: Optional[int] = LONG_MIN_BYTES
+    #: ... when the batch has at most this many rows
+    long_max_rows: int = LONG_MAX_ROWS
 
     def __init__(self, device: int = 0):
         self.device = device
         self._ctx = None
+
+    def _long(self, longest: Optional[int], n: int) -> Optional[int]:
+        """The ``max_len`` to call the long pair with, or None for the one-lane pair."""
+        if self.long_min_bytes is None or longest is None or longest < self.long_min_bytes or n > self.long_max_rows:
+            return None
+        if longest >> 31:
+            raise ValueError("AEAD rows are at most 2^31 - 1 bytes")
+        return max(int(longest), 1)
 
     @property
     def name(self) -> str:
@@ -223,28 +293,37 @@ class _GpuAEAD(SymmetricAlgorithm):
         return plain[0]
 
     # ------------------------------------------------------------------ batches
-    def encrypt_batch(self, keys, plaintexts, associated_data=None, nonces=None):
+    def encrypt_batch(self, keys, plaintexts, associated_data=None, nonces=None, max_len: Optional[int] = None):
         """Seal plaintexts[i] under keys[i]: row i = nonce || ciphertext || tag.
 
         ``keys``: [n, 32] uint8 (device tensor, numpy array or list of bytes).  ``plaintexts``: a list
         of byte strings (-> list of bytes), an [n, L] device tensor (-> [n, L + 28] device tensor) or
         :class:`PackedRows` (-> PackedRows).  ``associated_data``: None, one byte string for all rows,
         one per row, or a :class:`PackedInfos`.  ``nonces``: [n, 12] or None (OS CSPRNG); a caller
-        that supplies them must never reuse one under the same key."""
+        that supplies them must never reuse one under the same key.  ``max_len``: with PackedRows, the
+        caller's bound on any row's length, which lets the call take the long path (a row above it is
+        then left unwritten); for the other forms the host knows the longest row itself."""
         ctx = self._context()  # first: without a device this is the error to raise
+        longest = _longest(plaintexts)
         rows, kind = _rows_in(plaintexts, self.device)
         keys = _keys_dev(keys, rows.n, self.device)
         if nonces is not None and not _is_dev(nonces):
             nonces = _dev(_as_host(nonces, NONCE_LEN), self.device)
-        out = seal_rows(ctx, self._ALG, self.device, keys, rows, _aad(associated_data, rows.n, self.device),
-                        nonces)
+        aad = _aad(associated_data, rows.n, self.device)
+        bound = self._long(max_len if kind == "packed" else longest, rows.n)
+        if bound is None:
+            out = seal_rows(ctx, self._ALG, self.device, keys, rows, aad, nonces)
+        else:
+            out = seal_rows_long(ctx, self._ALG, self.device, keys, rows, aad, nonces, bound)
         return _rows_out(out, kind)
 
-    def decrypt_batch(self, keys, sealed, associated_data=None):
+    def decrypt_batch(self, keys, sealed, associated_data=None, max_len: Optional[int] = None):
         """Open sealed[i] under keys[i]: (plaintexts, status), status int32 [n] = 0, or -1 where the row
         is shorter than 28 bytes or does not verify.  Failed rows come back as zeros (a list row
         shorter than 28 bytes as b""): no unauthenticated plaintext is returned.  Input and output
-        forms as :meth:`encrypt_batch`; status is a numpy array for list input, else a device tensor."""
+        forms as :meth:`encrypt_batch`; status is a numpy array for list input, else a device tensor.
+        ``max_len``: with PackedRows, the bound on any row's plaintext length (as :meth:`encrypt_batch`;
+        a row above it gets status -1)."""
         ctx = self._context()
         short = None
         if not isinstance(sealed, PackedRows) and not _is_dev(sealed):
@@ -253,12 +332,17 @@ class _GpuAEAD(SymmetricAlgorithm):
             sealed = [bytes(x) for x in sealed]
             short = np.array([len(x) < OVERHEAD for x in sealed], dtype=bool)
             sealed = [bytes(OVERHEAD) if s else x for x, s in zip(sealed, short)]
+        longest = _longest(sealed, OVERHEAD)
         rows, kind = _rows_in(sealed, self.device)
         if kind == "matrix" and rows.n and rows.total // rows.n < OVERHEAD:
             raise ValueError(f"sealed rows must have at least {OVERHEAD} bytes")
         keys = _keys_dev(keys, rows.n, self.device)
-        out, status = open_rows(ctx, self._ALG, self.device, keys, rows,
-                                _aad(associated_data, rows.n, self.device))
+        aad = _aad(associated_data, rows.n, self.device)
+        bound = self._long(max_len if kind == "packed" else longest, rows.n)
+        if bound is None:
+            out, status = open_rows(ctx, self._ALG, self.device, keys, rows, aad)
+        else:
+            out, status = open_rows_long(ctx, self._ALG, self.device, keys, rows, aad, bound)
         if kind != "list":
             return _rows_out(out, kind), status
         status = status.cpu().numpy()
