@@ -204,14 +204,7 @@ int qrk_hqc_supports(qrk_ctx *ctx, const char *alg, int kind, size_t n, const ui
  * chunk for the algorithm (qrk_ctx_effective_chunk). */
 int qrk_hqc_code_decode(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *ct,
                         uint8_t *syms, uint8_t *mprime, void *stream);
-/* TEST HOOK, not for applications: qrk_hqc_code_decode (same contract, same limit on n) that also
- * returns the word the decoder is given.  t_out [n][n1 n2 / 8]: the n1 n2 bits of v - u y exactly as
- * the kernel hands them to the Reed-Muller stage, little-endian bytes as in the ciphertext's v.  The
- * sparse-dense product u y is otherwise visible only through a decoder that absorbs dozens of wrong
- * bits per block; stored by the production kernel's own code under a compile-time switch that is off
- * in every other call. */
-int qrk_dbg_hqc_decaps_trace(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *sk, const uint8_t *ct,
-                             uint8_t *t_out, uint8_t *syms, uint8_t *mprime, void *stream);
+/* (Its traced twin, the test hook qrk_dbg_hqc_decaps_trace, is declared in csrc/qrkem_debug.h.) */
 
 /* HKDF-SHA256 (RFC 5869) over n keys, one GPU lane per key.  Replaces
  * SecureMessaging._derive_symmetric_key (messaging.py:350-382: HKDF(SHA256,
@@ -322,21 +315,8 @@ int qrk_aead_seal_long_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint
 int qrk_aead_open_long_batch(qrk_ctx *ctx, const char *alg, size_t n, const uint8_t *keys, const uint8_t *sealed,
                              const uint64_t *sealed_off, const uint8_t *aad, const uint64_t *aad_off,
                              size_t aad_len, size_t max_len, uint8_t *pt, int32_t *status, void *stream);
-/* TEST HOOKS, not for applications (declared here beside qrk_dbg_hqc_decaps_trace: the hook header
- * csrc/qrkem_debug.h and its binding table are pinned at their present entries by tests/test_debug_abi.py).
- * The segment and tail kernels' MAC machinery of the long calls as a bare MAC under a caller-chosen
- * H (h [n][16]) or Poly1305 key32 = r | s ([n][32]), as qrk_dbg_ghash_batch / qrk_dbg_poly1305_batch of
- * csrc/qrkem_debug.h: device pointers, rows ragged by n + 1 offsets, whole 16-byte blocks (a trailing
- * partial block is ignored), rows above max_len left unwritten; out / tag [n][16].  Through the AEADs
- * H, r and s are cipher outputs and cannot be steered to their edge cases, and the block counts at which
- * a wrong power of the multiplier would show cannot be met with a chosen multiplier.
- * qrk_dbg_aead_long_residue: out[0] = the OR of every byte of the segment-partial region the context's
- * last long call (or hook) used; 0 after any completed call. */
-int qrk_dbg_ghash_long_batch(qrk_ctx *ctx, size_t n, const uint8_t *h, const uint8_t *data, const uint64_t *data_off,
-                             size_t max_len, uint8_t *out, void *stream);
-int qrk_dbg_poly1305_long_batch(qrk_ctx *ctx, size_t n, const uint8_t *key32, const uint8_t *msg,
-                                const uint64_t *msg_off, size_t max_len, uint8_t *tag, void *stream);
-int qrk_dbg_aead_long_residue(qrk_ctx *ctx, uint64_t *out);
+/* (The test hooks of the long calls, qrk_dbg_ghash_long_batch, qrk_dbg_poly1305_long_batch and
+ * qrk_dbg_aead_long_residue, are declared in csrc/qrkem_debug.h.) */
 
 /* ML-DSA signature verification (FIPS 204 final, "pure" ML-DSA: Verify, Algorithm 3), the step the
  * reference runs on every handshake and chat message (signatures.py:167 from messaging.py:721, 933,

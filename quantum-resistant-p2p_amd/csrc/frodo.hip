@@ -97,8 +97,6 @@ struct View {
   uint32_t* aesp;  // FrodoKEM-AES: per hs aes::prep_words<N>() words (round keys, round-2 parts)
 };
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 template <int N>
 size_t scratch_bytes_t(size_t C) {
   using P = FP<N>;
@@ -1088,9 +1086,6 @@ __global__ __launch_bounds__(64) void k_fr_kg_pkh_c(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- launchers
-inline unsigned blocks_for(size_t t, int per = 256) { return (unsigned)((t + per - 1) / per); }
-inline size_t round64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 inline bool coop_path(size_t n) { return n <= QRK_FR_COOP_MAX; }
 
 // SHAKE(domain || seedSE) sampler stream of W words per handshake
@@ -1253,7 +1248,7 @@ hipError_t frodo_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t 
 }
 
 size_t frodo_scratch_bytes(const AlgInfo& a, size_t chunk) {
-  const size_t C = frodo::round64(chunk);
+  const size_t C = round64(chunk);
   switch (a.k) {
     case 640: return frodo::scratch_bytes_t<640>(C);
     case 976: return frodo::scratch_bytes_t<976>(C);

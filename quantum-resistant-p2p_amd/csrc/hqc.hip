@@ -1310,8 +1310,6 @@ hipError_t supports_t(int kind, size_t n, const uint32_t* r, uint32_t* sup, hipS
 }
 
 // ---------------------------------------------------------------- launchers
-inline unsigned blocks_for(size_t t) { return (unsigned)((t + 255) / 256); }
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 template <int L>
 void launch_enc_expand(const uint8_t* m, size_t m_stride, const uint8_t* pk, size_t pk_stride, const uint8_t* salt,
                        size_t salt_stride, size_t n, uint64_t* row, hipStream_t st) {

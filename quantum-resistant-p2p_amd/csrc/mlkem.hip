@@ -59,11 +59,11 @@ namespace qrk {
 size_t mlkem_scratch_bytes(const AlgInfo& a, size_t chunk) {
   // the multi-workgroup KeyGen (n <= QRK_KG_MULTI_MAX) keeps one MkScr (16 KiB) per handshake in
   // the scratch; every other path needs scratch_words (about 5.1 KB per ML-KEM-768 handshake)
-  const size_t C = mlkem::round64(chunk);
+  const size_t C = round64(chunk);
   return std::max(mlkem::scratch_words(a.k, C) * 8, mlkem::keygen_scratch_bytes(C));
 }
 size_t mlkem_matrix_bytes(const AlgInfo& a, size_t chunk) {
-  return (size_t)a.k * a.k * mlkem::round64(chunk) * mlkem::XOF_W * sizeof(uint64_t);
+  return (size_t)a.k * a.k * round64(chunk) * mlkem::XOF_W * sizeof(uint64_t);
 }
 
 void mlkem_records_span(const AlgInfo& a, size_t C, size_t* off, size_t* bytes) {
@@ -76,7 +76,7 @@ void mlkem_records_span(const AlgInfo& a, size_t C, size_t* off, size_t* bytes) 
 hipError_t mlkem_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st) {
   // the one-launch kernels (n <= QRK_SMALL_MAX) keep their key material in LDS and wipe it
   if (n == 0 || n <= mlkem_small_max()) return hipSuccess;
-  const size_t C = mlkem::round64(n);
+  const size_t C = round64(n);
   const mlkem::ScratchView v = mlkem::carve(scratch, a.k, C);
   return hipMemsetAsync(v.seeds, 0, 16 * C * sizeof(uint64_t), st);  // seeds | mprime | kprime | kbar
 }

@@ -92,8 +92,5 @@ inline ScratchView carve(void* base, int K, size_t C) {
   return v;
 }
 
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
-inline size_t round64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 }  // namespace mlkem
 }  // namespace qrk

@@ -1,9 +1,8 @@
-// The library's test hooks: every exported qrk_dbg_* function that include/qrkem.h does not declare
-// (it declares qrk_dbg_hqc_decaps_trace and the three hooks of the long AEAD calls).  Not part of the public ABI: tests and tools call them
-// through ctypes, and qrkem/_debug.py holds their one binding table, which tests/test_debug_abi.py
-// checks against this file parameter by parameter.  abi.cpp, mlkem.hip and hqc.hip include it, so a
-// definition that drifts from its declaration does not compile.  Keep the declarations plain: pointers,
-// size_t, int and uint32_t parameters, an int result (0, or -1 with qrk_last_error() set).
+// The library's test hooks: every exported qrk_dbg_* function (include/qrkem.h declares none).  Not part of the
+// public ABI: tests and tools call them through ctypes, and qrkem/_debug.py holds their one binding table, which
+// tests/test_debug_abi.py checks against this file parameter by parameter.  The abi_*.cpp files, mlkem.hip and
+// hqc.hip include it, so a definition that drifts from its declaration does not compile.  Keep the declarations
+// plain: pointers, size_t, int and uint32_t parameters, an int result (0, or -1 with qrk_last_error() set).
 #pragma once
 #include "../../include/qrkem.h"
 
@@ -11,7 +10,7 @@
 extern "C" {
 #endif
 
-// -DQRK_HOST_TRACE=1 builds only (abi.cpp): the steady-clock stamps, in ns, at the phases of the last
+// -DQRK_HOST_TRACE=1 builds only (abi_kem.cpp): the steady-clock stamps, in ns, at the phases of the last
 // single-shot call, out[16] (tools/host_trace.py).
 #if QRK_HOST_TRACE
 int qrk_dbg_host_trace(long long* out);
@@ -61,6 +60,20 @@ int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, c
                            void* stream);
 int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                         void* stream);
+
+// The segment and tail kernels' MAC machinery of the long AEAD calls as a bare MAC under a caller-chosen
+// H (h [n][16]) or Poly1305 key32 = r | s ([n][32]), as qrk_dbg_ghash_batch / qrk_dbg_poly1305_batch above:
+// device pointers, rows ragged by n + 1 offsets, whole 16-byte blocks (a trailing
+// partial block is ignored), rows above max_len left unwritten; out / tag [n][16].  Through the AEADs
+// H, r and s are cipher outputs and cannot be steered to their edge cases, and the block counts at which
+// a wrong power of the multiplier would show cannot be met with a chosen multiplier.
+// qrk_dbg_aead_long_residue: out[0] = the OR of every byte of the segment-partial region the context's
+// last long call (or hook) used; 0 after any completed call.
+int qrk_dbg_ghash_long_batch(qrk_ctx* ctx, size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off,
+                             size_t max_len, uint8_t* out, void* stream);
+int qrk_dbg_poly1305_long_batch(qrk_ctx* ctx, size_t n, const uint8_t* key32, const uint8_t* msg,
+                                const uint64_t* msg_off, size_t max_len, uint8_t* tag, void* stream);
+int qrk_dbg_aead_long_residue(qrk_ctx* ctx, uint64_t* out);
 
 // qrk_mldsa_sign_batch with the loop's cap as an argument, which also writes, per row, mu [n][64] (zeros
 // for a row refused for its offsets or length) and the iterations run, iters [n] (0 for a refused row,
@@ -117,6 +130,15 @@ int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const u
 // only place a wrong mu' on such a row shows.
 int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                const uint8_t* sk, uint8_t* mu_out, void* stream);
+
+// qrk_hqc_code_decode (same contract, same limit on n) that also
+// returns the word the decoder is given.  t_out [n][n1 n2 / 8]: the n1 n2 bits of v - u y exactly as
+// the kernel hands them to the Reed-Muller stage, little-endian bytes as in the ciphertext's v.  The
+// sparse-dense product u y is otherwise visible only through a decoder that absorbs dozens of wrong
+// bits per block; stored by the production kernel's own code under a compile-time switch that is off
+// in every other call.
+int qrk_dbg_hqc_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* sk, const uint8_t* ct,
+                             uint8_t* t_out, uint8_t* syms, uint8_t* mprime, void* stream);
 
 #ifdef __cplusplus
 }

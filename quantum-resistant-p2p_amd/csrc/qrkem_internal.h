@@ -1,4 +1,4 @@
-// Internal host-side interface between the C-ABI (abi.cpp) and the kernel
+// Internal host-side interface between the C-ABI (abi_*.cpp) and the kernel
 // launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 // The exported test hooks (qrk_dbg_*) are declared in qrkem_debug.h and bound for ctypes in qrkem/_debug.py.
@@ -27,6 +27,12 @@ struct AlgInfo {
 
 const AlgInfo* find_alg(const char* name);
 
+// Size helpers of the host glue and the launchers: a slot rounded up to 256 bytes, a chunk rounded up to whole
+// 64-lane tiles, the grid of `threads` threads in workgroups of `per`.
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline size_t round64(size_t x) { return (x + 63) & ~(size_t)63; }
+inline unsigned blocks_for(size_t threads, int per = 256) { return (unsigned)((threads + per - 1) / per); }
+
 // Optional per-kernel HIP-event timing (qrk_ctx_profile): when a context has
 // profiling enabled, every QRK_LAUNCH brackets the launch with two events on the
 // launch stream; durations are summed per kernel name.
@@ -39,7 +45,7 @@ extern thread_local KernelTimer* g_timer;
 // First kernel-launch error of the current library call (HIP resets its last-error state on every
 // later successful API call, so a failed launch followed by successful ones would otherwise go
 // unnoticed).  The one error channel of the launchers: QRK_LAUNCH and qrk_chk record into it, every
-// launcher returns launch_status(), and only launch_begin() clears it.  An ABI call (abi.cpp: its
+// launcher returns launch_status(), and only launch_begin() clears it.  An ABI call (abi_ctx.h: its
 // CallScope, and run_batch / run_rows before each chunk) calls launch_begin() before it launches.
 // A launcher's return value is therefore the answer and there is no merge step for an entry point
 // to forget; the one thing left to forget is launch_begin(), and that reports an earlier call's
@@ -178,7 +184,7 @@ struct CtxState {
 
 // All pointers are device pointers; n handshakes processed as one chunk
 // (the caller splits large batches).  Return hipError_t.  The three families share one signature
-// per operation (abi.cpp keeps them in a table): `status` may be NULL, and a launcher that reports
+// per operation (abi_kem.cpp keeps them in a table): `status` may be NULL, and a launcher that reports
 // nothing ignores it.  ML-KEM Encaps writes status[i] = -1 when ek fails the FIPS 203 modulus check,
 // HQC Decaps when the re-encryption check fails (ss = K(sigma || ct) is still written, the
 // OQS_KEM_decaps return of liboqs), and both write 0 otherwise.

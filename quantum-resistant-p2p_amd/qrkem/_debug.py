@@ -1,7 +1,7 @@
 """ctypes signatures of the library's test hooks, the qrk_dbg_* functions csrc/qrkem_debug.h declares.
 
 Tests and tools only: ``qrkem/__init__.py`` does not import this module and the product path never
-calls a hook.  ``bind()`` is the one place outside ``_native._bind`` that sets ``argtypes`` on a
+calls a hook (``BatchKEM.hqc_decaps_trace``, a test helper, imports it when called).  ``bind()`` is the one place outside ``_native._bind`` that sets ``argtypes`` on a
 library function; tests/test_debug_abi.py checks the table against the header, name by name and
 parameter by parameter, so a hook cannot be called with a device pointer narrowed to a C int.
 """
@@ -24,6 +24,9 @@ HOOKS = {
     "qrk_dbg_mlkem_records_residue": (I, [P, ct.c_char_p, SZ, ct.POINTER(ct.c_uint64)]),
     "qrk_dbg_poly1305_batch": (I, [SZ, P, P, P, P, P]),
     "qrk_dbg_ghash_batch": (I, [SZ, P, P, P, P, P]),
+    "qrk_dbg_ghash_long_batch": (I, [P, SZ, P, P, P, SZ, P, P]),
+    "qrk_dbg_poly1305_long_batch": (I, [P, SZ, P, P, P, SZ, P, P]),
+    "qrk_dbg_aead_long_residue": (I, [P, ct.POINTER(ct.c_uint64)]),
     "qrk_dbg_mldsa_sign_trace": (I, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, U32, P, P, P]),
     "qrk_dbg_mldsa_verify_trace": (I, _VERIFY_TRACE),
     "qrk_dbg_mldsa_verify_keyed_trace": (I, [P, P, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]),
@@ -31,6 +34,7 @@ HOOKS = {
     "qrk_dbg_mldsa_keyed_sign_mode": (I, [I]),
     "qrk_dbg_slhdsa_verify_trace": (I, _VERIFY_TRACE),
     "qrk_dbg_frodo_decaps_trace": (I, [P, ct.c_char_p, SZ, P, P, P, P, P]),
+    "qrk_dbg_hqc_decaps_trace": (I, [P, ct.c_char_p, SZ, P, P, P, P, P, P]),
     "qrk_dbg_host_trace": (I, [ct.POINTER(ct.c_longlong)]),
     "qrk_dbg_ss_trace": (I, [ct.POINTER(ct.c_ulonglong)]),
     "qrk_dbg_hqc_trace": (I, [ct.POINTER(ct.c_ulonglong)]),

@@ -60,7 +60,6 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_digest_rows": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P]),
         "qrk_hqc_supports": (ct.c_int, [P, ct.c_char_p, ct.c_int, SZ, P, P, P]),
         "qrk_hqc_code_decode": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P]),
-        "qrk_dbg_hqc_decaps_trace": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, P]),
         "qrk_hkdf_sha256_batch": (ct.c_int, [P, SZ, P, SZ, P, SZ, P, P, SZ, P, SZ, P]),
         "qrk_handshake_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, SZ, P, P, P, P, P, P, P]),
         "qrk_aead_seal_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, P, SZ, P, P]),
@@ -68,9 +67,6 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_aead_long_layout": (ct.c_int, [ct.c_char_p, ct.POINTER(SZ)]),
         "qrk_aead_seal_long_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, P, SZ, SZ, P, P]),
         "qrk_aead_open_long_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, SZ, P, P, P]),
-        "qrk_dbg_ghash_long_batch": (ct.c_int, [P, SZ, P, P, P, SZ, P, P]),
-        "qrk_dbg_poly1305_long_batch": (ct.c_int, [P, SZ, P, P, P, SZ, P, P]),
-        "qrk_dbg_aead_long_residue": (ct.c_int, [P, ct.POINTER(ct.c_uint64)]),
         "qrk_sig_sizes": (ct.c_int, [ct.c_char_p, ct.POINTER(SZ)]),
         "qrk_sig_verify_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P]),
         "qrk_sig_keypair_batch": (ct.c_int, [P, ct.c_char_p, SZ, P, P, P, P]),

@@ -285,6 +285,7 @@ class BatchKEM:
         n1 = {16: 46, 24: 56, 32: 90}[k]
         vb = self.ct_len - 16 - (self.pk_len - 40)
         t, syms, mp = (self._empty(n, w).fill_(0xA5) for w in (vb, n1, k))
-        self._check(LIB.qrk_dbg_hqc_decaps_trace(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(t), _dptr(syms),
-                                                 _dptr(mp), self._stream()), "hqc_decaps_trace")
+        from ._debug import bind  # hooks are bound there, on first use: the product path never needs them
+        self._check(bind().qrk_dbg_hqc_decaps_trace(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(t),
+                                                    _dptr(syms), _dptr(mp), self._stream()), "hqc_decaps_trace")
         return t, syms, mp

@@ -1,15 +1,16 @@
-// Stand-alone host-memory check of the ML-DSA key-set entry points of csrc/abi.cpp: every path that returns
+// Stand-alone host-memory check of the ML-DSA key-set entry points of csrc/abi_sig.cpp: every path that returns
 // before any GPU work (load, info, argument refusals, free), meant to be built with the host sanitizers and run on
 // a machine without a GPU.  From the repository root:
 //
 //   F="--offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Iinclude"
 //   hipcc $F -c tests/mldsa_keyed_host_check.cpp -o build/host_check.o
-//   hipcc $F -fPIC -c quantum-resistant-p2p_amd/csrc/abi.cpp -o build/abi_san.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined build/host_check.o build/abi_san.o \
+//   for f in ctx kem aead sig util; do
+//     hipcc $F -fPIC -c quantum-resistant-p2p_amd/csrc/abi_$f.cpp -o build/abi_${f}_san.o; done
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined build/host_check.o build/abi_*_san.o \
 //         build/qrkem/{mlkem,util,frodo,hkdf,wire,hqc,aead,mldsa,mldsa_sign,mldsa_keyed,slhdsa,slhdsa_sign}.o \
 //         -o build/mldsa_keyed_host_check && build/mldsa_keyed_host_check
 //
-// (the kernel objects come from `make -C quantum-resistant-p2p_amd/csrc`; only abi.cpp and this file are
+// (the kernel objects come from `make -C quantum-resistant-p2p_amd/csrc`; only the abi_*.cpp files and this file are
 // instrumented).  Prints "ok" and exits 0; any sanitizer report or failed expectation exits nonzero.
 #include <cstdint>
 #include <cstdio>

@@ -11,6 +11,7 @@ import pytest
 import aead_spec
 import make_golden_aead_long as gen
 from test_abi import declared_functions, exported_symbols
+from test_debug_abi import DEBUG_HEADER
 
 ALGS = aead_spec.ALGS
 CALLS = {"qrk_aead_long_layout": 2, "qrk_aead_seal_long_batch": 13, "qrk_aead_open_long_batch": 13}
@@ -23,11 +24,17 @@ def golden(golden_dir):
 
 
 def test_symbols_exported_declared_and_bound():
-    """The calls and their three test hooks are in the header, in the binding table and in the library."""
+    """The calls are in the public header and its binding table, their three test hooks in the hook header and
+    its table (and in no other), and all six in the library."""
+    from qrkem import _debug
     from qrkem._native import LIB
-    exported, declared = exported_symbols(), declared_functions()
+    exported = exported_symbols()
+    public, hooks = declared_functions(), declared_functions(DEBUG_HEADER)
+    assert _debug.bind() is LIB
     for name, nargs in {**CALLS, **HOOKS}.items():
-        assert name in exported and name in declared, name
+        assert name in exported, name
+        assert (name in hooks and name not in public) if name in HOOKS else (name in public and name not in hooks), name
+        assert (name in _debug.HOOKS) == (name in HOOKS), name
         fn = getattr(LIB, name)
         assert fn.restype is ct.c_int and fn.argtypes is not None and len(fn.argtypes) == nargs, name
 
@@ -91,7 +98,8 @@ def test_argument_checks_in_the_documented_order_without_a_device(call):
 
 def test_hooks_check_their_arguments_without_a_device():
     import qrkem
-    from qrkem._native import LIB
+    from qrkem._debug import bind
+    LIB = bind()
     one = ct.c_void_p(1)
     for fn in (LIB.qrk_dbg_ghash_long_batch, LIB.qrk_dbg_poly1305_long_batch):
         assert fn(None, 1, one, one, one, 16, one, None) == -1 and "null context" in qrkem.last_error()

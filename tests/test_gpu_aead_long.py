@@ -45,9 +45,9 @@ def ptr(t):
 
 
 def residue(ctx) -> int:
-    from qrkem._native import LIB
+    from qrkem._debug import bind
     out = ct.c_uint64(123)
-    assert LIB.qrk_dbg_aead_long_residue(ctx, ct.byref(out)) == 0
+    assert bind().qrk_dbg_aead_long_residue(ctx, ct.byref(out)) == 0
     return out.value
 
 
@@ -178,11 +178,11 @@ def mac_rows(seed):
 
 def run_hook(ctx, name, key, rows, max_len):
     from qrkem import last_error
-    from qrkem._native import LIB
+    from qrkem._debug import bind
     n = len(rows)
     out = torch.full((16 * n,), FILL, dtype=torch.uint8, device="cuda")
     k, d, o = dev(key * n), dev(b"".join(rows)), offsets(rows)
-    assert getattr(LIB, name)(ctx, n, ptr(k), ptr(d), ptr(o), max_len, ptr(out), None) == 0, last_error()
+    assert getattr(bind(), name)(ctx, n, ptr(k), ptr(d), ptr(o), max_len, ptr(out), None) == 0, last_error()
     torch.cuda.synchronize()
     return split(out.cpu().numpy().tobytes(), [16] * n, 0)
 

@@ -274,8 +274,10 @@ def test_chunk_below_batch(alg):
 def test_trace_rejects_oversize_batch_and_unknown_algorithm():
     """More records than the context chunk, a name that is no parameter set and a parameter set
     that is not HQC are errors, and nothing is launched: the outputs keep their fill."""
-    from qrkem._native import LIB, last_error
+    from qrkem._debug import bind
+    from qrkem._native import last_error
     from qrkem.batch import BatchKEM
+    LIB = bind()
     eng = BatchKEM("HQC-128", device=0, chunk=64)
     n = eng.effective_chunk + 1
     sk = torch.zeros((n, eng.sk_len), dtype=torch.uint8, device="cuda")

@@ -98,7 +98,7 @@ def test_device_keypair_then_frodo_host_encaps_without_sync():
 
 def test_host_single_shot_then_device_calls_without_sync():
     """Host-pointer calls run on the context's I/O stream, device-pointer calls on the torch
-    stream; each waits for the other through the context's last-use event (abi.cpp LastUse /
+    stream; each waits for the other through the context's last-use event (abi_ctx.h LastUse /
     ctx_order).  Single-shot host calls (the pipelined KeyGen uses the context scratch)
     interleaved with device-pointer calls, no synchronize in between, then a host batch large
     enough to regrow the pinned mirror (ctx_quiesce): every output byte-exact vs the oracle."""

@@ -136,8 +136,12 @@ def test_single_bit_products_have_their_closed_form(alg):
 
 
 def test_trace_hook_is_exported_and_declared_as_a_test_hook():
-    from test_abi import HEADER, declared_functions, exported_symbols
-    assert "qrk_dbg_hqc_decaps_trace" in exported_symbols() and "qrk_dbg_hqc_decaps_trace" in declared_functions()
-    text = HEADER.read_text()
-    comment = text[:text.index("int qrk_dbg_hqc_decaps_trace")].rsplit("/*", 1)[1]
-    assert "TEST HOOK" in comment
+    """Exported, declared in the hook header (whose first line says what it holds) and not in the public one,
+    and bound in the hooks' table."""
+    from qrkem import _debug
+    from test_abi import declared_functions, exported_symbols
+    from test_debug_abi import DEBUG_HEADER
+    name = "qrk_dbg_hqc_decaps_trace"
+    assert name in exported_symbols() and name in declared_functions(DEBUG_HEADER)
+    assert name not in declared_functions() and name in _debug.HOOKS
+    assert "test hooks" in DEBUG_HEADER.read_text().splitlines()[0]

@@ -12,7 +12,9 @@ mkdir -p "$O" "$R/quantum-resistant-p2p_amd/qrkem/variants"
 for f in $(cd "$C" && ls *.hip | sed "s/\.hip$//"); do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 "$@" -c "$C/$f.hip" -o "$O/$f.o" &
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -fPIC -std=c++17 "$@" -c "$C/abi.cpp" -o "$O/abi.o" &
+for f in $(cd "$C" && ls abi_*.cpp | sed "s/\.cpp$//"); do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -fPIC -std=c++17 "$@" -c "$C/$f.cpp" -o "$O/$f.o" &
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/quantum-resistant-p2p_amd/qrkem/variants/libqrkem_$tag.so" "$O"/*.o
 echo "built variants/libqrkem_$tag.so"

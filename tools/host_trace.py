@@ -2,7 +2,7 @@
 """Where the host side of one single-shot OQS call goes (a -DQRK_HOST_TRACE=1 build):
     tools/build_variant.sh htrace -DQRK_HOST_TRACE=1
     QRKEM_LIBRARY=quantum-resistant-p2p_amd/qrkem/variants/libqrkem_htrace.so python3 tools/host_trace.py
-Stamps (abi.cpp HT(i)): 0 single() entry, 1 context locked, 2 inputs staged in the pinned mirror,
+Stamps (abi_kem.cpp HT(i)): 0 single() entry, 1 context locked, 2 inputs staged in the pinned mirror,
 3 run_batch ready to launch, 4 launch call returned, 5 run_batch returned (its end event recorded),
 6 completion ticket seen, 7 outputs copied out + mirror wiped, 9 single() returns.  Also the Python
 call time around it.  Median microseconds over N calls, one JSON line per operation."""
