@@ -698,6 +698,15 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   return 0;
 }
 
+// test hook (qrkem_debug.h): the handshake driver's key compare on chosen rows
+int qrk_dbg_keys_equal(size_t n, const uint8_t* a, const uint8_t* b, size_t len, int32_t* agree, void* stream) {
+  if (n && (!a || !b || !agree)) return fail("null buffer");
+  if (len == 0 || len > 255 * 32) return fail("key length must be 1..8160 bytes");
+  launch_begin();  // no context, so no scope
+  hipError_t e = keys_equal(n, a, b, len, agree, (hipStream_t)stream);
+  return hip_done("keys_equal", e);
+}
+
 // test hook (qrkem_debug.h): qrk_kem_decaps_batch for a FrodoKEM parameter set that also writes mu'
 int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                const uint8_t* sk, uint8_t* mu_out, void* stream) {

@@ -61,6 +61,13 @@ int qrk_dbg_poly1305_batch(size_t n, const uint8_t* key32, const uint8_t* msg, c
 int qrk_dbg_ghash_batch(size_t n, const uint8_t* h, const uint8_t* data, const uint64_t* data_off, uint8_t* out,
                         void* stream);
 
+// The handshake driver's key compare (k_keys_equal) on chosen rows: agree_i = 1 iff a_i == b_i, a and b
+// [n][len] device bytes, len 1..8160 as the driver's key_len, agree [n].  Through qrk_handshake_batch both
+// keys come out of the same KEM and HKDF, so honest handshakes never disagree and the word bench.py counts
+// as key_disagreements cannot be made 0 there: a compare that ignored a byte, or strode rows wrongly, shows
+// only on inputs that differ in one chosen bit.
+int qrk_dbg_keys_equal(size_t n, const uint8_t* a, const uint8_t* b, size_t len, int32_t* agree, void* stream);
+
 // The segment and tail kernels' MAC machinery of the long AEAD calls as a bare MAC under a caller-chosen
 // H (h [n][16]) or Poly1305 key32 = r | s ([n][32]), as qrk_dbg_ghash_batch / qrk_dbg_poly1305_batch above:
 // device pointers, rows ragged by n + 1 offsets, whole 16-byte blocks (a trailing

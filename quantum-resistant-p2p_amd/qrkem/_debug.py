@@ -24,6 +24,7 @@ HOOKS = {
     "qrk_dbg_mlkem_records_residue": (I, [P, ct.c_char_p, SZ, ct.POINTER(ct.c_uint64)]),
     "qrk_dbg_poly1305_batch": (I, [SZ, P, P, P, P, P]),
     "qrk_dbg_ghash_batch": (I, [SZ, P, P, P, P, P]),
+    "qrk_dbg_keys_equal": (I, [SZ, P, P, SZ, P, P]),
     "qrk_dbg_ghash_long_batch": (I, [P, SZ, P, P, P, SZ, P, P]),
     "qrk_dbg_poly1305_long_batch": (I, [P, SZ, P, P, P, SZ, P, P]),
     "qrk_dbg_aead_long_residue": (I, [P, ct.POINTER(ct.c_uint64)]),
