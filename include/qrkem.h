@@ -436,6 +436,47 @@ int qrk_mldsa_sign_keyed_batch(qrk_ctx *ctx, const qrk_mldsa_keyset *ks, size_t 
                                const uint8_t *msg, const uint64_t *msg_off, const uint8_t *rnd,
                                const uint8_t *ctx_str, size_t ctx_len, uint8_t *sig, int32_t *status, void *stream);
 
+/* ML-KEM key sets: many rows under few keys.  A service with a long-lived KEM key decapsulates everything sent to
+ * that key, and a node encapsulates to one peer key many times; qrk_kem_encaps_batch / qrk_kem_decaps_batch redo
+ * per row what depends on the key alone (SampleNTT for the whole matrix A_hat, H(ek), Encaps' modulus check).  A
+ * key set holds g keys expanded once, and the keyed calls take an index into it per row.
+ *
+ * Load: pk [g][pk bytes] or sk [g][sk bytes], device pointers; *out receives the handle.  The expansion is
+ * stream-ordered on `stream`: calls that use the set on another stream must be ordered behind it by the caller,
+ * and `pk` / `sk` may be released once that stream has passed the load.  Checked before any device work, in this
+ * order: null context, name (anything but the three ML-KEM names: -1, a FrodoKEM or HQC name with "key sets are
+ * ML-KEM only", any other with "unsupported KEM"), g == 0, null pointers, g beyond what the context's scratch
+ * budget rule allows for one allocation (and 2^32 - 1).  An ek that fails the FIPS 203 modulus check loads all the
+ * same and is marked: rows that name it return what qrk_kem_encaps_batch returns for it, status -1 included.
+ * A set holds 2372 / 4676 / 7748 (public: A_hat, ek, H(ek), the mark) or 3168 / 5856 / 9312 (secret: A_hat, dk)
+ * bytes of device memory per key for ML-KEM-512 / 768 / 1024, plus at most 1 KiB of alignment per set.  A secret
+ * set holds the dk bytes of its keys: next to the caller's sk rows it is the only long-lived place in device
+ * memory with secret-derived bytes.  qrk_mlkem_keyset_free synchronises the device, zeroes the whole allocation
+ * and then frees it (NULL: no-op); free a set before the device is reset.  qrk_ctx_cleanse does not touch key sets.
+ * qrk_mlkem_keyset_info: out = { g, parameter set (0, 1, 2 = ML-KEM-512, 768, 1024), 1 if secret, device bytes held }. */
+typedef struct qrk_mlkem_keyset qrk_mlkem_keyset;
+int qrk_mlkem_pubkeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *pk, qrk_mlkem_keyset **out,
+                           void *stream);
+int qrk_mlkem_seckeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *sk, qrk_mlkem_keyset **out,
+                           void *stream);
+int qrk_mlkem_keyset_info(const qrk_mlkem_keyset *ks, size_t out[4]);
+void qrk_mlkem_keyset_free(qrk_mlkem_keyset *ks);
+/* Encaps / Decaps under a key set: row i uses key key_index[i] (uint32 [n], a device pointer; NULL means "every
+ * row uses key 0" and is accepted only when g == 1); every other argument as in qrk_kem_encaps_batch /
+ * qrk_kem_decaps_batch_status (coins NULL: the OS CSPRNG; status NULL: not reported), and so are the results: byte
+ * for byte what those calls return for the same keys and coins.  An index >= g is checked on the device before
+ * anything is addressed with it and makes the row a refused one: status -1 and an all-zero ct / ss row; its
+ * neighbours are untouched.  No step's work depends on whether a ciphertext is valid or a row refused.  Checked
+ * before any device work, in this order: null context; a null or foreign key set (loaded on another device than
+ * the context's, or a public set passed to Decaps / a secret set to Encaps), with a message that says which; then
+ * n == 0 returns 0; then null buffers.  Rows run in chunks of the context's chunk; the scratch grows by 1088 /
+ * 1472 / 1856 bytes per row (ML-KEM-512 / 768 / 1024: PRF words, seeds, m', K', Kbar -- no matrix), and the four
+ * secret records are zeroed behind every chunk. */
+int qrk_mlkem_encaps_keyed_batch(qrk_ctx *ctx, const qrk_mlkem_keyset *ks, size_t n, const uint32_t *key_index,
+                                 uint8_t *ct, uint8_t *ss, const uint8_t *coins, int32_t *status, void *stream);
+int qrk_mlkem_decaps_keyed_batch(qrk_ctx *ctx, const qrk_mlkem_keyset *ks, size_t n, const uint32_t *key_index,
+                                 uint8_t *ss, const uint8_t *ct, int32_t *status, void *stream);
+
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853
  * ciphertext and responder key; decoded at :829 with base64.b64decode).  Device pointers,

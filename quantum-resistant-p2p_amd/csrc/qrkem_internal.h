@@ -1,5 +1,5 @@
 // Internal host-side interface between the C-ABI (abi_*.cpp) and the kernel
-// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
+// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, mlkem_keyed.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 // The exported test hooks (qrk_dbg_*) are declared in qrkem_debug.h and bound for ctypes in qrkem/_debug.py.
 #pragma once
@@ -194,6 +194,36 @@ hipError_t mlkem_encaps(const AlgInfo& a, size_t n, uint8_t* ct, uint8_t* ss, co
                         const uint8_t* coins, int32_t* status, void* scratch, const Streams& st);
 hipError_t mlkem_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
                         int32_t* status, void* scratch, const Streams& st);
+
+// ML-KEM key sets (mlkem_keyed.hip): g keys expanded once into one device allocation of mlkem_keyset_bytes, and
+// Encaps / Decaps of n rows that name their key by index.  MlkemKeys is the view of that allocation
+// (mlkem_keyset_view; device pointers): A_hat, one contiguous 384-byte entry of 12-bit coefficients per
+// (key, x, y), [g][k k][384]; the key bytes [g][stride], ek rows for a public set and dk rows (secret: they hold
+// s_hat and z) for a secret one; a public set adds H(ek) [g][32] and a word per key that is nonzero where ek
+// fails the FIPS 203 modulus check.  key_index [n] (device; NULL: every row uses key 0) is checked against g on
+// the device before any address is formed from it: a row with an index >= g gets status -1 and an all-zero ct /
+// ss row.  Everything else as mlkem_encaps / mlkem_decaps, whose bytes these return.  The scratch
+// (mlkem_keyed_scratch_bytes) holds the PRF words and seeds | m' | K' | Kbar per row and no matrix;
+// mlkem_keyed_cleanse zeroes the four records after every chunk.
+struct MlkemKeys {
+  uint32_t g = 0;
+  const void* A = nullptr;
+  const uint8_t* keys = nullptr;
+  size_t stride = 0;
+  const void* h = nullptr;
+  const uint32_t* bad = nullptr;
+};
+size_t mlkem_keyset_bytes(const AlgInfo& a, bool secret, size_t g);
+MlkemKeys mlkem_keyset_view(const AlgInfo& a, bool secret, size_t g, void* mem);
+// keys: pk [g][pk] or sk [g][sk]; mem: mlkem_keyset_bytes, every byte of it is written
+hipError_t mlkem_keyset_expand(const AlgInfo& a, bool secret, size_t g, const uint8_t* keys, void* mem,
+                               hipStream_t st);
+size_t mlkem_keyed_scratch_bytes(const AlgInfo& a, size_t chunk);
+hipError_t mlkem_keyed_cleanse(const AlgInfo& a, size_t n, void* scratch, hipStream_t st);
+hipError_t mlkem_encaps_keyed(const AlgInfo& a, const MlkemKeys& ks, size_t n, const uint32_t* key_index, uint8_t* ct,
+                              uint8_t* ss, const uint8_t* coins, int32_t* status, void* scratch, const Streams& s);
+hipError_t mlkem_decaps_keyed(const AlgInfo& a, const MlkemKeys& ks, size_t n, const uint32_t* key_index, uint8_t* ss,
+                              const uint8_t* ct, int32_t* status, void* scratch, const Streams& s);
 
 hipError_t frodo_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
                          void* scratch, const Streams& st);

@@ -25,7 +25,15 @@ _SYMMETRIC = ("SymmetricAlgorithm", "AES256GCM", "ChaCha20Poly1305")
 _SIGNATURES = ("SignatureAlgorithm", "MLDSASignature", "MLDSASigner", "MLDSAKeySet", "SPHINCSSignature")
 
 
+# ML-KEM key sets (batch.py over mlkem_keyed.hip): BatchKEM.load_public_keys / encaps_keyed and their secret halves
+_BATCH = ("BatchKEM", "MLKEMKeySet")
+
+
 def __getattr__(name: str):
+    if name in _BATCH or name == "batch":
+        import importlib
+        mod = importlib.import_module(".batch", __name__)
+        return mod if name == "batch" else getattr(mod, name)
     if name in _SYMMETRIC or name == "symmetric":
         import importlib
         mod = importlib.import_module(".symmetric", __name__)

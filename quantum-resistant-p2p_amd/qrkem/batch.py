@@ -36,6 +36,11 @@ def _dptr(t) -> ct.c_void_p:
     return ct.c_void_p(t.data_ptr())
 
 
+def _kptr(t) -> Optional[ct.c_void_p]:
+    """A key_index device tensor (any 32-bit dtype), or None."""
+    return None if t is None else ct.c_void_p(t.data_ptr())
+
+
 def _check_dev(t, width: int, what: str, n: Optional[int] = None):
     """Device [n, width] uint8 contiguous, like _as_host's check for host arrays: the kernels
     index rows at the fixed stride `width`, so a wrong shape must fail here, not read past
@@ -63,6 +68,57 @@ def _as_host(x, width: int) -> np.ndarray:
     if a.ndim != 2 or a.shape[1] != width:
         raise ValueError(f"expected a [n, {width}] uint8 array, got shape {a.shape}")
     return a
+
+
+class MLKEMKeySet:
+    """g ML-KEM keys expanded once on the device (``qrk_mlkem_pubkeys_load`` / ``qrk_mlkem_seckeys_load``,
+    mlkem_keyed.hip): what :meth:`BatchKEM.encaps_keyed` and :meth:`BatchKEM.decaps_keyed` index into.  Made by
+    :meth:`BatchKEM.load_public_keys` / :meth:`BatchKEM.load_secret_keys`; owns the handle and is a context
+    manager.  A secret set holds the dk bytes in device memory until :meth:`close`, which zeroes them (the
+    library synchronises the device first)."""
+
+    def __init__(self, handle, alg: str, g: int, secret: bool, device: int = 0):
+        self._handle = handle
+        self.alg = alg
+        self.g = int(g)
+        self.secret = bool(secret)
+        self.device = device
+
+    @property
+    def closed(self) -> bool:
+        return not self._handle
+
+    @property
+    def device_bytes(self) -> int:
+        """Bytes of device memory the set holds (``qrk_mlkem_keyset_info``); 0 once closed."""
+        if self.closed:
+            return 0
+        out = (ct.c_size_t * 4)()
+        if LIB.qrk_mlkem_keyset_info(self._handle, out) != 0:
+            raise RuntimeError(last_error())
+        return int(out[3])
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            LIB.qrk_mlkem_keyset_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self) -> str:
+        kind = "secret" if self.secret else "public"
+        return f"<MLKEMKeySet {self.alg} {kind} g={self.g}{' closed' if self.closed else ''}>"
 
 
 class BatchKEM:
@@ -184,6 +240,107 @@ class BatchKEM:
         st = np.zeros((s.shape[0],), np.int32)
         self._check(LIB.qrk_kem_decaps_batch_status_host(self._ctx, self._name, s.shape[0], _hptr(ss), _hptr(c),
                                                          _hptr(s), _hptr(st)), "decaps")
+        return (ss, st) if return_status else ss
+
+    # ------------------------------------------------------------------ key sets (ML-KEM)
+    def _keyed_only(self) -> None:
+        if not self.alg.startswith("ML-KEM-"):
+            raise ValueError(f"key sets are ML-KEM only: {self.alg} has none (use encaps / decaps)")
+
+    def _load_keys(self, keys, width: int, secret: bool) -> MLKEMKeySet:
+        self._keyed_only()
+        what = "secret" if secret else "public"
+        if not _is_dev(keys):
+            keys = torch.from_numpy(_as_host(keys, width)).to(f"cuda:{self.device}")
+        _check_dev(keys, width, f"{what} keys")
+        g = keys.shape[0]
+        if g == 0:
+            raise ValueError(f"a key set holds at least one {what} key")
+        h = ct.c_void_p()
+        load = LIB.qrk_mlkem_seckeys_load if secret else LIB.qrk_mlkem_pubkeys_load
+        self._check(load(self._ctx, self._name, g, _dptr(keys), ct.byref(h), self._stream()), "key set load")
+        torch.cuda.current_stream(self.device).synchronize()  # the set is ready on every stream; `keys` may go
+        return MLKEMKeySet(h, self.alg, g, secret, self.device)
+
+    def load_public_keys(self, pk) -> MLKEMKeySet:
+        """A key set of the g encapsulation keys pk [g, pk_len] (a device tensor, numpy array or list of bytes):
+        SampleNTT for A_hat, H(ek) and the FIPS 203 modulus check run once per key here and never again per row."""
+        return self._load_keys(pk, self.pk_len, False)
+
+    def load_secret_keys(self, sk) -> MLKEMKeySet:
+        """A key set of the g decapsulation keys sk [g, sk_len]: SampleNTT for A_hat runs once per key here."""
+        return self._load_keys(sk, self.sk_len, True)
+
+    def _keyed_args(self, keyset, secret: bool, key_index, n: int):
+        if not isinstance(keyset, MLKEMKeySet):
+            raise ValueError("keyset must be an MLKEMKeySet")
+        if keyset.alg != self.alg:
+            raise ValueError(f"the key set holds {keyset.alg} keys, this object is {self.alg}")
+        if keyset.secret and not secret:
+            raise ValueError("a secret key set cannot encapsulate: load the public keys with load_public_keys")
+        if secret and not keyset.secret:
+            raise ValueError("a public key set cannot decapsulate: load the secret keys with load_secret_keys")
+        if keyset.device != self.device:
+            raise ValueError(f"the key set is on device {keyset.device}, this object on device {self.device}")
+        if key_index is None and keyset.g != 1:
+            raise ValueError(f"key_index may be None only for a key set of one key, this one has {keyset.g}")
+        if keyset.closed:
+            raise ValueError("the key set is closed")
+        if key_index is None:
+            return None
+        if not _is_dev(key_index):
+            idx = np.asarray(key_index)
+            if idx.ndim != 1 or idx.dtype.kind not in "iu" or (idx.size and (idx.min() < 0 or idx.max() >= 2 ** 32)):
+                raise ValueError("key_index must be a 1-D sequence of n indices in [0, 2^32)")
+            key_index = torch.from_numpy(idx.astype(np.uint32).view(np.int32)).to(f"cuda:{self.device}")
+        if key_index.dtype == torch.int64:
+            key_index = key_index.to(torch.int32)  # an index of 2^31 or more is outside every set either way
+        if not (key_index.dim() == 1 and key_index.numel() == n and key_index.is_contiguous() and
+                key_index.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+            raise ValueError("key_index must be a contiguous 1-D 32-bit device tensor of n entries")
+        return key_index
+
+    def encaps_keyed(self, keyset, key_index=None, n: Optional[int] = None, coins=None, return_status: bool = False):
+        """Encaps of n rows under a public key set: row i uses key ``key_index[i]`` (None: key 0 of a set of one).
+        n comes from key_index, coins or ``n``.  Returns device (ct, ss) (+ status int32[n]: -1 where the key
+        fails the FIPS 203 7.2 check or the index is outside the set -- that row's ct and ss are zero): byte for
+        byte what :meth:`encaps` returns for the same keys and coins."""
+        self._keyed_only()
+        if key_index is not None:
+            n = len(key_index) if not _is_dev(key_index) else key_index.numel()
+        elif coins is not None:
+            n = len(coins) if not _is_dev(coins) else coins.shape[0]
+        if n is None:
+            raise ValueError("give key_index, coins or n")
+        key_index = self._keyed_args(keyset, False, key_index, n)
+        dev = f"cuda:{self.device}"
+        if coins is not None and not _is_dev(coins):
+            coins = torch.from_numpy(_as_host(coins, self.enc_coins)).to(dev)
+        if coins is not None:
+            _check_dev(coins, self.enc_coins, "encaps coins", n)
+        c, ss = self._empty(n, self.ct_len), self._empty(n, self.ss_len)
+        st = torch.empty((n,), dtype=torch.int32, device=dev) if return_status else None
+        self._check(LIB.qrk_mlkem_encaps_keyed_batch(self._ctx, keyset._handle, n,
+                                                     _kptr(key_index), _dptr(c), _dptr(ss),
+                                                     _dptr(coins) if coins is not None else None,
+                                                     _dptr(st) if st is not None else None, self._stream()),
+                    "encaps_keyed")
+        return (c, ss, st) if return_status else (c, ss)
+
+    def decaps_keyed(self, keyset, ct_, key_index=None, return_status: bool = False):
+        """Decaps of the rows ct [n, ct_len] under a secret key set: row i uses key ``key_index[i]``.  Returns
+        device ss [n, ss_len] (+ status int32[n]: 0, or -1 with a zero ss row where the index is outside the set;
+        an invalid ciphertext is rejected implicitly, status 0): byte for byte what :meth:`decaps` returns."""
+        self._keyed_only()
+        if not _is_dev(ct_):
+            ct_ = torch.from_numpy(_as_host(ct_, self.ct_len)).to(f"cuda:{self.device}")
+        n = _check_dev(ct_, self.ct_len, "decaps ct").shape[0]
+        key_index = self._keyed_args(keyset, True, key_index, n)
+        ss = self._empty(n, self.ss_len)
+        st = torch.empty((n,), dtype=torch.int32, device=ct_.device) if return_status else None
+        self._check(LIB.qrk_mlkem_decaps_keyed_batch(self._ctx, keyset._handle, n, _kptr(key_index), _dptr(ss),
+                                                     _dptr(ct_), _dptr(st) if st is not None else None,
+                                                     self._stream()), "decaps_keyed")
         return (ss, st) if return_status else ss
 
     @property
