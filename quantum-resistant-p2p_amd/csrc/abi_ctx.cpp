@@ -134,18 +134,36 @@ int qrk_ctx_create(qrk_ctx** out, int device) {
   return 0;
 }
 
-// Zero every buffer of the context that can hold keys or secret intermediates (device scratch,
-// handshake scratch, device and pinned host staging).  Synchronous.
-static void cleanse_all(qrk_ctx* ctx) {
+// Every buffer of the context that can hold keys or secret intermediates (device scratch, handshake
+// scratch, device and pinned host staging) set to `byte` over its full current size.  Synchronous.
+// The one list of those buffers: cleanse_all (byte 0) and the test hook qrk_dbg_ctx_fill walk it.
+// What a call relies on from one call to the next is not in it: the ML-KEM CtxState words, hflag,
+// preloaded key sets (they own their memory), and the sizes, aead_long_part among them.
+static hipError_t fill_all(qrk_ctx* ctx, int byte) {
   ctx_quiesce(ctx);
-  if (ctx->scratch) (void)hipMemset(ctx->scratch, 0, ctx->scratch_bytes);
-  if (ctx->hs_scratch) (void)hipMemset(ctx->hs_scratch, 0, ctx->hs_scratch_bytes);
-  if (ctx->dio) (void)hipMemset(ctx->dio, 0, ctx->dio_bytes);
-  if (ctx->dstage) (void)hipMemset(ctx->dstage, 0, ctx->dstage_bytes);
-  (void)hipDeviceSynchronize();
-  if (ctx->hio) OQS_MEM_cleanse(ctx->hio, ctx->hio_bytes);
-  if (ctx->hstage) OQS_MEM_cleanse(ctx->hstage, ctx->hstage_bytes);
+  void* const dev[] = {ctx->scratch, ctx->hs_scratch, ctx->dio, ctx->dstage};
+  const size_t dev_bytes[] = {ctx->scratch_bytes, ctx->hs_scratch_bytes, ctx->dio_bytes, ctx->dstage_bytes};
+  uint8_t* const pinned[] = {ctx->hio, ctx->hstage};
+  const size_t pinned_bytes[] = {ctx->hio_bytes, ctx->hstage_bytes};
+  hipError_t first = hipSuccess;
+  for (int i = 0; i < 4; ++i) {
+    if (!dev[i]) continue;
+    const hipError_t e = hipMemset(dev[i], byte, dev_bytes[i]);
+    if (first == hipSuccess) first = e;
+  }
+  const hipError_t e = hipDeviceSynchronize();
+  if (first == hipSuccess) first = e;
+  for (int i = 0; i < 2; ++i) {
+    if (!pinned[i]) continue;
+    if (byte == 0) {
+      OQS_MEM_cleanse(pinned[i], pinned_bytes[i]);
+    } else {
+      memset(pinned[i], byte, pinned_bytes[i]);
+    }
+  }
+  return first;
 }
+static void cleanse_all(qrk_ctx* ctx) { (void)fill_all(ctx, 0); }
 
 int qrk_ctx_cleanse(qrk_ctx* ctx) {
   if (!ctx) return fail("null context");
@@ -215,6 +233,12 @@ int qrk_dbg_kg_late(int role) {
 int qrk_dbg_fail_launch(int on) {
   g_dbg_fail_launch.store(on, std::memory_order_relaxed);
   return 0;
+}
+
+int qrk_dbg_ctx_fill(qrk_ctx* ctx, int byte) {
+  CallScope scope;
+  if (open_inspect(scope, ctx, byte >= 0 && byte <= 255)) return -1;
+  return hip_done("hipMemset(context fill)", fill_all(ctx, byte));
 }
 
 int qrk_dbg_fail_after_flip(int on) {

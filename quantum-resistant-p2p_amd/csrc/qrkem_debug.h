@@ -38,6 +38,14 @@ int qrk_dbg_kg_late(int role);
 // valid buffers, except where a launcher stops at the first failure.  Process-wide.
 int qrk_dbg_fail_launch(int on);
 
+// Writes `byte` (0..255) over the full current size of every buffer qrk_ctx_cleanse zeroes: the scratch,
+// the handshake scratch, dio, dstage and the pinned hio / hstage (one list, walked by both).  Synchronous,
+// after the previous call's device work.  What a call relies on from one call to the next is left alone:
+// the ML-KEM counter words, the single-shot flag, preloaded key sets, and the record of which region the
+// last long AEAD call used.  The next call then finds, in every word it does not write itself, a value no
+// earlier call of the same shape would have left there (tests/test_gpu_ctx_fill.py).
+int qrk_dbg_ctx_fill(qrk_ctx* ctx, int byte);
+
 // Batched ML-KEM Encaps / Decaps chunks of at most 2^15 handshakes fail right after the SampleNTT
 // fix-up counter parity flip, before their first launch (0: off), and the context's two fix-up
 // counter words and its parity read back (the re-zero path).

@@ -18,6 +18,7 @@ _VERIFY_TRACE = [P, ct.c_char_p, SZ, P, P, P, P, P, SZ, P, P, P, P, P, P]
 HOOKS = {
     "qrk_dbg_kg_late": (I, [I]),
     "qrk_dbg_fail_launch": (I, [I]),
+    "qrk_dbg_ctx_fill": (I, [P, I]),
     "qrk_dbg_fail_after_flip": (I, [I]),
     "qrk_dbg_fixc_words": (I, [P, ct.POINTER(U32), ct.POINTER(I)]),
     "qrk_dbg_kg_flags_residue": (I, [P, ct.POINTER(ct.c_uint64)]),
