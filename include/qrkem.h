@@ -131,6 +131,14 @@ int qrk_ctx_staging_residue(qrk_ctx *ctx, uint64_t out[3]);
 /* Handshakes per chunk actually used for `alg` (FrodoKEM and HQC cap the chunk so their
  * scratch stays within QRK_SCRATCH_GIB = 48 GiB); 0 for an unknown algorithm. */
 size_t qrk_ctx_effective_chunk(const qrk_ctx *ctx, const char *alg);
+/* What a context keeps of a batched ML-KEM KeyGen for its own Decaps of the same keys: the sampled
+ * matrix A_hat (K^2 384 bytes per handshake) and a 32-byte rho tag per handshake, of whole batched
+ * chunks (more than 1024 rows) in order, as many as the cap allows.  For a KeyGen of n handshakes on a
+ * context whose chunk is `chunk`: out[0] = rows per chunk, out[1] = batched chunks, out[2] = chunks
+ * kept, out[3] = bytes kept.  cap_bytes = (size_t)-1: the cap in force, QRK_KEEP_MIB MiB from the
+ * environment (read at every KeyGen; 0 keeps nothing), 8192 by default.  Pure arithmetic, no device.
+ * Outputs never depend on what is kept, only time does. */
+int qrk_mlkem_keep_plan(const char *alg, size_t n, size_t chunk, size_t cap_bytes, size_t out[4]);
 /* Schedule of one operation's kernels, all on the caller's stream: 0 (default): independent
  * kernels share multi-role launches (each role's workgroups a contiguous range of one grid, in
  * grid order); 1: serial, one kernel per launch (kernel timings in isolation).  Any other value

@@ -138,15 +138,19 @@ int qrk_ctx_create(qrk_ctx** out, int device) {
 // scratch, device and pinned host staging) set to `byte` over its full current size.  Synchronous.
 // The one list of those buffers: cleanse_all (byte 0) and the test hook qrk_dbg_ctx_fill walk it.
 // What a call relies on from one call to the next is not in it: the ML-KEM CtxState words, hflag,
-// preloaded key sets (they own their memory), and the sizes, aead_long_part among them.
+// preloaded key sets (they own their memory), and the sizes, aead_long_part among them.  The ML-KEM kept
+// region (public data) is in it, and is invalid from here: no later Decaps reads what this wrote there.
 static hipError_t fill_all(qrk_ctx* ctx, int byte) {
   ctx_quiesce(ctx);
-  void* const dev[] = {ctx->scratch, ctx->hs_scratch, ctx->dio, ctx->dstage};
-  const size_t dev_bytes[] = {ctx->scratch_bytes, ctx->hs_scratch_bytes, ctx->dio_bytes, ctx->dstage_bytes};
+  void* keep = nullptr;
+  size_t keep_bytes = 0;
+  ctx->mlkem.keep_invalidate(&keep, &keep_bytes);
+  void* const dev[] = {ctx->scratch, ctx->hs_scratch, ctx->dio, ctx->dstage, keep};
+  const size_t dev_bytes[] = {ctx->scratch_bytes, ctx->hs_scratch_bytes, ctx->dio_bytes, ctx->dstage_bytes, keep_bytes};
   uint8_t* const pinned[] = {ctx->hio, ctx->hstage};
   const size_t pinned_bytes[] = {ctx->hio_bytes, ctx->hstage_bytes};
   hipError_t first = hipSuccess;
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < 5; ++i) {
     if (!dev[i]) continue;
     const hipError_t e = hipMemset(dev[i], byte, dev_bytes[i]);
     if (first == hipSuccess) first = e;

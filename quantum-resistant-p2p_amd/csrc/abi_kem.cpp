@@ -101,8 +101,8 @@ struct CallOpts {
   bool flag = false;                  // single-shot: the kernel stores ctx->ticket in the completion flag ...
   const uint8_t* host_in1 = nullptr;  // ... and may take the public input's host copy as a by-value argument
   bool kg_err = false;                // ML-KEM KeyGen: hand the launch the error word, hflag[1]
-  uint64_t* xof_keep = nullptr;       // Streams::xof_keep (KeyGen) / xof_given (Decaps): the handshake
-  const uint64_t* xof_given = nullptr;  // driver's A_hat hand-over
+  bool no_keep = false;               // ML-KEM KeyGen: leave the context's kept region as it is (the handshake
+                                      // driver's responder keys, which this context never decapsulates under)
   uint8_t* frodo_mu = nullptr;        // FrodoKEM Decaps (tests): mu' [n][32], copied out before each chunk's cleanse
 };
 
@@ -140,19 +140,34 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     S.ticket = ctx->ticket;
     S.host_in1 = opts.host_in1;
   }
+  bool keeps = false;
   if (a.family == Family::MLKEM) {
     if (opts.kg_err) S.kg_err = ctx->hflag_dev + 1;
-    S.xof_keep = opts.xof_keep;
-    S.xof_given = opts.xof_given;
     const char* what = nullptr;
     const hipError_t e = ctx->mlkem.prepare(S, op, n, chunk, ctx->scratch, ctx->scratch_bytes, &what);
     if (e != hipSuccess) return hip_fail(what, e);
+    // KeyGen keeps its sampled matrices for this context's Decaps of the same keys (CtxState, the kept
+    // region): invalid from here until every chunk is queued, so a failed KeyGen leaves none
+    // (a KeyGen of one-launch chunks alone neither writes the region nor looks at it)
+    keeps = op == Op::KEYPAIR && !opts.no_keep && n > mlkem_small_max();
+    if (keeps) {
+      struct Wait {
+        qrk_ctx* ctx;
+        hipStream_t st;
+      } w{ctx, st};
+      ctx->mlkem.keep_begin(a, n, chunk, mlkem_keep_cap_bytes(), [](void* p) {
+        ctx_quiesce(((Wait*)p)->ctx);
+        (void)hipStreamSynchronize(((Wait*)p)->st);
+      }, &w);
+    }
   }
   HT(3);
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = std::min(chunk, n - off);
     hipError_t e = hipSuccess;
     launch_begin();
+    if (keeps) ctx->mlkem.keep_chunk(S, off / chunk);
+    if (a.family == Family::MLKEM && op == Op::DECAPS) ctx->mlkem.kept_chunk(S, a, chunk, off / chunk, m);
     int32_t* const stat = status ? status + off : nullptr;
     switch (op) {
       case Op::KEYPAIR:
@@ -179,6 +194,7 @@ static int run_batch(qrk_ctx* ctx, const AlgInfo& a, Op op, size_t n, uint8_t* o
     e = f.cleanse(a, m, ctx->scratch, st);
     if (e != hipSuccess) return hip_fail("hipMemsetAsync(cleanse)", e);
   }
+  if (keeps) ctx->mlkem.keep_commit();
   return 0;
 }
 
@@ -535,6 +551,17 @@ size_t qrk_ctx_effective_chunk(const qrk_ctx* ctx, const char* alg) {
   return chunk_for(ctx, *a);
 }
 
+int qrk_mlkem_keep_plan(const char* alg, size_t n, size_t chunk, size_t cap_bytes, size_t out[4]) {
+  const AlgInfo* a = find_alg(alg);
+  if (!a || a->family != Family::MLKEM) return fail("not an ML-KEM algorithm");
+  if (!out || chunk == 0) return fail("bad argument");
+  const size_t rows = n ? chunk_plan(n, round64(chunk)) : 0;
+  const KeepPlan p = mlkem_keep_plan(mlkem_matrix_bytes(*a, 64) / 64, n, rows, mlkem_small_max(),
+                                     cap_bytes == (size_t)-1 ? mlkem_keep_cap_bytes() : cap_bytes);
+  out[0] = rows, out[1] = p.batched, out[2] = p.kept, out[3] = p.bytes;
+  return 0;
+}
+
 int qrk_kem_sizes(const char* alg, size_t out[6]) {
   const AlgInfo* a = find_alg(alg);
   if (!a) return fail(std::string("unsupported KEM: ") + (alg ? alg : "(null)"));
@@ -650,14 +677,12 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
   const size_t chunk = chunk_for(ctx, *a);
   const size_t m0 = std::min(chunk, n);
   const size_t b_sk = al256(m0 * a->sk), b_ss = al256(m0 * a->ss);
-  // ML-KEM batched chunks: the initiator's sampled matrix A_hat, kept from its KeyGen (:590) for its
-  // Decaps (:1038) -- the same rho, so Decaps skips K^2 SampleNTT entries (27 of a handshake's ~174
-  // ML-KEM-768 permutations).  Public data (a function of rho): outside the wiped range.
-  const bool keep_a = a->family == Family::MLKEM && m0 > mlkem_small_max();
-  const size_t b_mat = keep_a ? al256(mlkem_matrix_bytes(*a, m0)) : 0;
-  if (grow_device(ctx, (void**)&ctx->hs_scratch, &ctx->hs_scratch_bytes, 2 * b_sk + 2 * b_ss + b_mat, st)) return -1;
+  // ML-KEM batched chunks: the initiator's sampled matrix A_hat stays in the context's kept region from
+  // its KeyGen (:590) for its Decaps (:1038) -- the same rho, so Decaps skips K^2 SampleNTT entries (27 of
+  // a handshake's ~174 ML-KEM-768 permutations).  The region's own budget decides whether it is kept; a
+  // batch never fails for it.  The responder's KeyGen in between leaves the region alone.
+  if (grow_device(ctx, (void**)&ctx->hs_scratch, &ctx->hs_scratch_bytes, 2 * b_sk + 2 * b_ss, st)) return -1;
   uint8_t *sk_i = ctx->hs_scratch, *sk_r = sk_i + b_sk, *ss_i = sk_r + b_sk, *ss_r = ss_i + b_ss;
-  uint64_t* mat_i = keep_a ? (uint64_t*)(ss_r + b_ss) : nullptr;
   // wipes the ephemeral sk / ss on every exit path, error returns included (runs before the
   // scope records the end of the call)
   struct Wipe {
@@ -670,14 +695,14 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
     const size_t m = std::min(chunk, n - off);
     auto co = [&](const uint8_t* c, size_t len) { return c ? c + off * len : nullptr; };
     // initiate_key_exchange: ephemeral KeyGen (messaging.py:590); A_hat kept for its Decaps
-    CallOpts kg_opts, dec_opts;
-    dec_opts.xof_given = kg_opts.xof_keep = (keep_a && m > mlkem_small_max()) ? mat_i : nullptr;
     if (run_batch(ctx, *a, Op::KEYPAIR, m, pk_i + off * a->pk, sk_i, co(coins_kp_i, a->kp_coins), nullptr, nullptr, st,
-                  kg_opts))
+                  {}))
       return -1;
     // _handle_key_exchange_init: responder KeyGen (:809, pk sent back at :853) + Encaps (:830)
+    CallOpts responder;
+    responder.no_keep = true;
     if (run_batch(ctx, *a, Op::KEYPAIR, m, pk_r + off * a->pk, sk_r, co(coins_kp_r, a->kp_coins), nullptr, nullptr,
-                  st, {}))
+                  st, responder))
       return -1;
     if (run_batch(ctx, *a, Op::ENCAPS, m, ct + off * a->ct, ss_r, pk_i + off * a->pk, co(coins_enc, a->enc_coins),
                   nullptr, st, {}))
@@ -686,7 +711,7 @@ int qrk_handshake_batch(qrk_ctx* ctx, const char* alg, size_t n, const uint8_t* 
                                info_len, key_len, key_r + off * key_len, key_len, st);  // :845
     if (e != hipSuccess) return hip_fail("hkdf_sha256", e);
     // _handle_key_exchange_response: Decaps (:1038) + HKDF (:1068)
-    if (run_batch(ctx, *a, Op::DECAPS, m, ss_i, nullptr, ct + off * a->ct, sk_i, nullptr, st, dec_opts)) return -1;
+    if (run_batch(ctx, *a, Op::DECAPS, m, ss_i, nullptr, ct + off * a->ct, sk_i, nullptr, st, {})) return -1;
     e = hkdf_sha256(m, ss_i, a->ss, a->ss, nullptr, 0, info, info_off ? info_off + off : nullptr, info_len,
                     key_len, key_i + off * key_len, key_len, st);
     if (e != hipSuccess) return hip_fail("hkdf_sha256", e);

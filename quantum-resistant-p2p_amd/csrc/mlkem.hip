@@ -28,7 +28,7 @@
 // Where the code is.  This file: the entry points qrkem_internal.h declares, i.e. the sizes, the
 // cleanse and the dispatch between the execution paths.  One file per path, each with its kernels
 // and plain host launchers (mlkem_paths.h), included below:
-//   mlkem_batch.cuh   n > 1024: k_front_keygen, k_back_keygen, k_rho_copy, k_keygen_core, the roles
+//   mlkem_batch.cuh   n > 1024: k_front_keygen, k_back_keygen, k_rho_copy, k_rho_match, k_keygen_core, the roles
 //                     (RXof, RXofFixCoop, RFrontEnc[Pair], RJDec, RGDec[Pair], RPrf, RDecrypt, RCore)
 //                     with k_multi / k_role, rho_source, and the per-context state (mlkem::CtxState)
 //   mlkem_one.cuh     n <= 1024: k_encaps_one, k_decaps_one, k_keygen_one; qrk_dbg_ss_trace
@@ -64,6 +64,11 @@ size_t mlkem_scratch_bytes(const AlgInfo& a, size_t chunk) {
 }
 size_t mlkem_matrix_bytes(const AlgInfo& a, size_t chunk) {
   return (size_t)a.k * a.k * round64(chunk) * mlkem::XOF_W * sizeof(uint64_t);
+}
+
+size_t mlkem_keep_cap_bytes() {
+  const char* v = std::getenv("QRK_KEEP_MIB");
+  return (size_t)((v && *v) ? std::strtoull(v, nullptr, 10) : 8192) << 20;
 }
 
 void mlkem_records_span(const AlgInfo& a, size_t C, size_t* off, size_t* bytes) {

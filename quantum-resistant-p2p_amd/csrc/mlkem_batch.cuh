@@ -178,6 +178,30 @@ __global__ __launch_bounds__(256) void k_rho_copy(const uint8_t* __restrict__ ba
   if (t >= 4 * n) return;
   out[t] = ((const uint64_t*)(base + (t >> 2) * stride))[t & 3];
 }
+// The same copy for a Decaps chunk whose KeyGen's matrix the context kept, with the match pass folded in:
+// a row matches where the rho in its dk equals tags[row], the rho KeyGen stored beside the row's kept
+// entries (rows below kept_rows; any row beyond them, a permuted row or a key from elsewhere misses), and
+// hit[row] = 1 where all four rows of its aligned quad match.  The quad is what one wave of the
+// re-encryption core holds (16 lanes per handshake), so the core's choice of matrix is wave-uniform and
+// its base stays in scalar registers; a row that matched in a quad that missed is sampled like its
+// neighbours, which is always right.  rho is public, so the compare may be what it is.  Four lanes per
+// row, a quad's sixteen in one wave.
+__global__ __launch_bounds__(256) void k_rho_match(const uint8_t* __restrict__ base, size_t stride, size_t n,
+                                                   const uint64_t* __restrict__ tags, size_t kept_rows,
+                                                   uint64_t* __restrict__ out, uint32_t* __restrict__ hit,
+                                                   uint32_t* __restrict__ nfix) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;  // one thread per word
+  if (t == 0) *nfix = 0;
+  const size_t row = t >> 2;
+  bool eq = false;
+  if (row < n) {
+    const uint64_t w = ((const uint64_t*)(base + row * stride))[t & 3];
+    out[t] = w;
+    if (row < kept_rows) eq = w == tags[t];
+  }
+  const uint64_t m = __ballot(eq);
+  if (row < n && (t & 3) == 0) hit[row] = ((m >> (threadIdx.x & 48)) & 0xFFFF) == 0xFFFF;
+}
 
 // ------------------------------------------------------------ KeyGen core
 // s_hat = NTT(CBD(PRF(sigma, j))), e_hat = NTT(CBD(PRF(sigma, k+i))),
@@ -251,17 +275,28 @@ __global__ __launch_bounds__(256) void k_keygen_core(size_t n, size_t C, const u
 // ------------------------------------------------------------ K-PKE.Encrypt core
 // MODE 0 (encaps): write c.  MODE 1 (decaps): compare c' with the input c and
 // select K' or Kbar in constant time (FIPS 203 Alg. 18 lines 9-11).
+// MODE 1 with hit != NULL (a chunk whose KeyGen's matrix the context kept): a wave whose handshakes' hit
+// word is set reads its matrix entries from xof_kept, the others from xof (k_rho_match; rho is public).
 template <int K, int MODE>
-__device__ __forceinline__ void encrypt_core_hs(size_t n, size_t C, const uint64_t* __restrict__ xof,
+__device__ __forceinline__ void encrypt_core_hs(size_t n, size_t C, const uint64_t* __restrict__ xof_own,
                                                       const uint64_t* __restrict__ prf,
                                                       const uint8_t* __restrict__ ek_base, size_t ek_stride,
                                                       const uint8_t* __restrict__ m_base, size_t m_stride,
                                                       uint8_t* __restrict__ ct, int32_t* __restrict__ status,
                                                       const uint64_t* __restrict__ kprime,
-                                                      const uint64_t* __restrict__ kbar, uint8_t* __restrict__ ss, size_t hs_raw, int L, GroupLds& g) {
+                                                      const uint64_t* __restrict__ kbar, uint8_t* __restrict__ ss,
+                                                      const uint64_t* __restrict__ xof_kept,
+                                                      const uint32_t* __restrict__ hit, size_t hs_raw, int L,
+                                                      GroupLds& g) {
   constexpr int DU = P<K>::DU, DV = P<K>::DV;
   const bool active = hs_raw < n;
   const size_t hs = active ? hs_raw : n - 1;  // index in the chunk
+  const uint64_t* xof = xof_own;
+  if constexpr (MODE == 1) {
+    // the four handshakes of a wave are one quad of k_rho_match (a clamped lane's hs is in the quad or
+    // the whole wave is clamped to n - 1): one value per wave
+    if (hit && __builtin_amdgcn_readfirstlane(hit[hs])) xof = xof_kept;
+  }
   const uint8_t* ek = ek_base + hs * ek_stride;
   uint8_t* c = ct + hs * P<K>::CT;
   uint32_t diff = 0;
@@ -567,10 +602,12 @@ struct RCore {  // K-PKE.Encrypt (MODE 1: the Decaps re-encryption, compare and 
   const uint64_t *kprime, *kbar;
   uint8_t* ss;
   unsigned nb;
+  const uint64_t* xof_kept = nullptr;  // MODE 1: the kept matrix and the per-handshake hit words
+  const uint32_t* hit = nullptr;       // (k_rho_match), NULL: every handshake reads xof
   __device__ __forceinline__ void run(unsigned vb, char* lds) const {
     const int gi = threadIdx.x >> 4;
     encrypt_core_hs<K, MODE>(n, C, xof, prf, ek, ek_stride, m_base, m_stride, ct, status, kprime, kbar, ss,
-                             (size_t)vb * GROUPS + gi, threadIdx.x & 15, ((GroupLds*)lds)[gi]);
+                             xof_kept, hit, (size_t)vb * GROUPS + gi, threadIdx.x & 15, ((GroupLds*)lds)[gi]);
   }
 };
 
@@ -722,9 +759,6 @@ hipError_t CtxState::prepare(Streams& S, Op op, size_t n, size_t chunk, void* sc
   } else {
     S.kg_err = nullptr;
   }
-  const bool one_batched_chunk = n <= chunk && n > mlkem_small_max();
-  if (!one_batched_chunk || op != Op::KEYPAIR) S.xof_keep = nullptr;
-  if (!one_batched_chunk || op != Op::DECAPS) S.xof_given = nullptr;
   if (op != Op::KEYPAIR) {
     if (!fixc) {
       *what = "hipMalloc(fixc)";
@@ -762,6 +796,59 @@ void CtxState::keygen_failed(bool pipe_call, void* scratch, size_t scratch_bytes
 void CtxState::free() {
   if (kg_cnt) (void)hipFree(kg_cnt);
   if (fixc) (void)hipFree(fixc);
+  if (keep) (void)hipFree(keep);
+}
+
+// ---- the kept region (qrkem_internal.h: what it is, and the rule that keeps a stale one from being read)
+static KeepPlan keep_plan_of(int k, size_t n, size_t chunk, size_t cap_bytes) {
+  return mlkem_keep_plan((size_t)k * k * XOF_W * sizeof(uint64_t), n, chunk, mlkem_small_max(), cap_bytes);
+}
+
+void CtxState::keep_begin(const AlgInfo& a, size_t n, size_t chunk, size_t cap_bytes, void (*quiesce)(void*),
+                          void* arg) {
+  keep_valid = false;
+  const KeepPlan p = keep_plan_of(a.k, n, chunk, cap_bytes);
+  keep_k = a.k, keep_n = n, keep_chunk_rows = chunk, keep_chunks = p.kept;
+  if (p.bytes <= keep_bytes) return;
+  if (keep) {  // public data: nothing to wipe, but an earlier call may still read it
+    quiesce(arg);
+    (void)hipFree(keep);
+    keep = nullptr, keep_bytes = 0;
+  }
+  if (hipMalloc((void**)&keep, p.bytes) == hipSuccess) {
+    keep_bytes = p.bytes;
+  } else {
+    (void)hipGetLastError();  // not this call's error: the KeyGen runs as it would without the region
+    keep = nullptr, keep_chunks = 0;
+  }
+}
+
+void CtxState::keep_chunk(Streams& S, size_t idx) const {
+  S.xof_keep = S.rho_keep = nullptr;
+  if (idx >= keep_chunks) return;
+  const KeepPlan p = keep_plan_of(keep_k, keep_n, keep_chunk_rows, (size_t)-1);
+  S.rho_keep = (uint64_t*)(keep + idx * p.chunk_bytes);
+  S.xof_keep = (uint64_t*)(keep + idx * p.chunk_bytes + p.tag_bytes);
+}
+
+void CtxState::keep_commit() { keep_valid = keep_chunks > 0; }
+
+void CtxState::kept_chunk(Streams& S, const AlgInfo& a, size_t chunk, size_t idx, size_t m) const {
+  S.xof_kept = S.rho_kept = nullptr;
+  S.kept_rows = 0;
+  if (!keep_valid || a.k != keep_k || chunk != keep_chunk_rows || idx >= keep_chunks) return;
+  // the rows KeyGen's chunk idx held; the tiled layout is a function of round64(rows)
+  const size_t rows = std::min(keep_chunk_rows, keep_n - idx * keep_chunk_rows);
+  if (m <= mlkem_small_max() || round64(m) != round64(rows)) return;
+  const KeepPlan p = keep_plan_of(keep_k, keep_n, keep_chunk_rows, (size_t)-1);
+  S.rho_kept = (const uint64_t*)(keep + idx * p.chunk_bytes);
+  S.xof_kept = (const uint64_t*)(keep + idx * p.chunk_bytes + p.tag_bytes);
+  S.kept_rows = rows;
+}
+
+void CtxState::keep_invalidate(void** p, size_t* bytes) {
+  keep_valid = false;
+  *p = keep, *bytes = keep_bytes;
 }
 
 hipError_t CtxState::fix_words(uint32_t* out, int* parity, const char** what) const {
@@ -814,7 +901,9 @@ hipError_t keygen_impl(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins,
   const size_t C = round64(n);
   ScratchView v = carve(scratch, K, C);
   hipStream_t st = s.main;
-  if (s.xof_keep) v.xof = s.xof_keep;  // the handshake driver keeps A_hat for the same party's Decaps
+  // the context keeps A_hat, and each row's rho as its tag, for the same party's Decaps (the front writes
+  // the compact rho copy SampleNTT reads: here it is the tags)
+  if (s.xof_keep && s.rho_keep) v.xof = s.xof_keep, v.rho = s.rho_keep;
   QRK_LAUNCH("k_front_keygen", st, k_front_keygen<K>, dim3(blocks_for(n)), dim3(256), 0, st, coins, n, pk, sk,
              v.seeds, v.rho, v.nfix);
   const uint8_t* rho = (const uint8_t*)v.rho;
@@ -852,7 +941,8 @@ hipError_t encaps_impl(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, co
 }
 
 // Decaps: rho copy -> {J(z || c), K-PKE.Decrypt, SampleNTT} -> G(m' || h) -> {SampleNTT fix-up, PRFs}
-// -> re-encryption with the constant-time compare and select
+// -> re-encryption with the constant-time compare and select.  Under a kept matrix (s.xof_kept) the rho
+// copy is k_rho_match and SampleNTT runs for the rows that missed alone.
 template <int K>
 hipError_t decaps_impl(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk, void* scratch,
                        const Streams& s) {
@@ -864,30 +954,38 @@ hipError_t decaps_impl(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* 
   const RJDec<K> jd{ct, sk, n, v.kbar, blocks_for(n)};
   const RGDec<K> gd{sk, v.mprime, n, v.seeds, v.kprime, blocks_for(n)};
   const RPrf<P<K>::ETA1, P<K>::ETA2> prf{v.seeds, n, C, 2 * K + 1, K, v.prf, blocks_for((2 * K + 1) * C)};
-  if (s.xof_given) {  // A_hat from this party's KeyGen (handshake driver): no SampleNTT, no fix-up
-    const RCore<K, 1> core{n, C, s.xof_given, v.prf, sk + 384 * K, (size_t)P<K>::SK, (const uint8_t*)v.mprime,
-                           (size_t)32, const_cast<uint8_t*>(ct), nullptr, v.kprime, v.kbar, ss, gblocks};
-    launch_multi("k_j_decaps+k_decrypt_core", {"k_j_decaps", "k_decrypt_core"}, s, jd, dec);
-    if (C <= QRK_PAIR_FRONT_MAX)
-      launch_one("k_g_decaps", RGDecPair<K>{sk, v.mprime, n, v.seeds, v.kprime, blocks_for(2 * n)}, s);
-    else
-      launch_one("k_g_decaps", gd, s);
-    launch_one("k_prf", prf, s);
-    launch_one("k_encrypt_core", core, s);
-    return launch_status();
-  }
   poison_xof<K>(C, v, st);
-  const RhoSrc rho = rho_source(sk + 768 * K, (size_t)P<K>::SK, n, C, v, s);
+  // A_hat from this party's KeyGen on this context (s.xof_kept): the match pass rides on the rho copy, at
+  // every chunk size, and the launches below are the usual ones under other names (k_xof_miss: the
+  // SampleNTT role's lanes return where their row hit, so a wave whose rows all hit retires at once; only
+  // rows that ran reach the fix-up list; the core takes each handshake's matrix base from its hit word).
+  // Nothing is read back: which rows hit is known on the device alone.  The same launches serve the caller
+  // whose dk buffer is the very one KeyGen wrote: pointer equality would prove nothing the match pass does
+  // not establish, and a role of empty workgroups costs microseconds.
+  const bool kept = s.xof_kept && s.rho_kept;
+  RhoSrc rho;
+  if (kept) {
+    QRK_LAUNCH("k_rho_match", st, k_rho_match, dim3(blocks_for(4 * n)), dim3(256), 0, st, sk + 768 * K,
+               (size_t)P<K>::SK, n, s.rho_kept, s.kept_rows, v.rho, v.hit, v.nfix);
+    rho = {(const uint8_t*)v.rho, 32, v.nfix, nullptr};
+  } else {
+    rho = rho_source(sk + 768 * K, (size_t)P<K>::SK, n, C, v, s);
+  }
   if (launch_status() != hipSuccess) return launch_status();  // nothing after a failed step
-  const RCore<K, 1> core{n, C, v.xof, v.prf, sk + 384 * K, (size_t)P<K>::SK, (const uint8_t*)v.mprime, (size_t)32,
-                         const_cast<uint8_t*>(ct), nullptr, v.kprime, v.kbar, ss, gblocks};
+  RCore<K, 1> core{n, C, v.xof, v.prf, sk + 384 * K, (size_t)P<K>::SK, (const uint8_t*)v.mprime, (size_t)32,
+                   const_cast<uint8_t*>(ct), nullptr, v.kprime, v.kbar, ss, gblocks};
+  RXof<K, false> xof = xof_role<K>(rho, n, C, v);
+  if (kept) core.xof_kept = s.xof_kept, core.hit = xof.a.hit = v.hit;
   // J stays one lane per handshake: at chunks <= 2^15 its launch, {J, decrypt core, SampleNTT}, is
   // throughput-bound, and J on lane pairs (1.3x the issue slots) ran it 105.3 -> 118.7 us at 2^14
   // (47.2e6 against 45.5e6 handshakes/s, profiles/r5/pair_fronts/abx_2p14_pairJ_noJ_off.jsonl); J split
   // over this launch and the next (its last two permutations beside the fix-up and the PRFs) took
   // 4 us off this launch and added 3-14 us to the next: no gain (profiles/r5/mid/)
-  launch_multi("k_j_decaps+k_decrypt_core+k_xof", {"k_j_decaps", "k_decrypt_core", "k_xof"}, s, jd, dec,
-               xof_role<K>(rho, n, C, v));
+  if (kept)
+    launch_multi("k_j_decaps+k_decrypt_core+k_xof_miss", {"k_j_decaps", "k_decrypt_core", "k_xof_miss"}, s, jd, dec,
+                 xof);
+  else
+    launch_multi("k_j_decaps+k_decrypt_core+k_xof", {"k_j_decaps", "k_decrypt_core", "k_xof"}, s, jd, dec, xof);
   if (C <= QRK_PAIR_FRONT_MAX)
     launch_one("k_g_decaps", RGDecPair<K>{sk, v.mprime, n, v.seeds, v.kprime, blocks_for(2 * n)}, s);
   else

@@ -65,10 +65,11 @@ struct ScratchView {
   uint64_t *xof, *prf, *seeds, *mprime, *kprime, *kbar;
   uint32_t *fix, *nfix;  // SampleNTT fix-up list (entries needing > 3 blocks, capacity K^2 C), its counter
   uint64_t* rho;         // every handshake's rho, 32 B apart (k_rho_copy)
+  uint32_t* hit;         // Decaps under a kept matrix: a word per handshake, 1 = its rho matched (k_rho_match)
 };
 __host__ __device__ inline size_t scratch_words(int K, size_t C) {
   return (size_t)K * K * C * XOF_W + (size_t)(2 * K + 1) * C * PRF_W + 16 * C + ((size_t)K * K * C + 16) / 2 + 4 +
-         4 * C;
+         4 * C + C / 2;
 }
 inline ScratchView carve(void* base, int K, size_t C) {
   ScratchView v;
@@ -89,6 +90,8 @@ inline ScratchView carve(void* base, int K, size_t C) {
   v.fix = v.nfix + 16;
   p += ((size_t)K * K * C + 16) / 2 + 4;
   v.rho = p;
+  p += 4 * C;
+  v.hit = (uint32_t*)p;
   return v;
 }
 

@@ -156,6 +156,9 @@ struct XofArgs {
   XUnit* out;
   uint32_t *fix, *nfix;  // the fix-up list and its counter
   uint32_t* zero_other;  // main pass (chunks <= DIRECT_RHO_MAX): the counter the next call counts into
+  // main pass of a Decaps chunk under a kept matrix: per-handshake hit words (k_rho_match), a lane whose
+  // row hit has nothing to sample; NULL: every entry is sampled
+  const uint32_t* hit = nullptr;
 };
 // block vb of nvb (FIX: the grid-stride walk over the list uses nvb)
 template <int K, bool FIX>
@@ -166,6 +169,7 @@ __device__ __forceinline__ void xof_body(const XofArgs<K, FIX>& a, unsigned vb, 
     if (vb == 0 && threadIdx.x == 0 && a.zero_other) *a.zero_other = 0u;
     const size_t e = (size_t)vb * 256 + threadIdx.x, hs = e % a.C;
     if (e >= (size_t)K * K * a.C || hs >= a.n) return;
+    if (a.hit && a.hit[hs]) return;  // rho is public
     const int xy = (int)(e / a.C);
     const size_t inst = (size_t)xy * a.C + hs;
     KState s;

@@ -39,7 +39,8 @@ int qrk_dbg_kg_late(int role);
 int qrk_dbg_fail_launch(int on);
 
 // Writes `byte` (0..255) over the full current size of every buffer qrk_ctx_cleanse zeroes: the scratch,
-// the handshake scratch, dio, dstage and the pinned hio / hstage (one list, walked by both).  Synchronous,
+// the handshake scratch, dio, dstage, the ML-KEM kept region (which is invalid from then on: no later Decaps
+// reads the fill) and the pinned hio / hstage (one list, walked by both).  Synchronous,
 // after the previous call's device work.  What a call relies on from one call to the next is left alone:
 // the ML-KEM counter words, the single-shot flag, preloaded key sets, and the record of which region the
 // last long AEAD call used.  The next call then finds, in every word it does not write itself, a value no

@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <type_traits>
 
@@ -138,15 +139,44 @@ struct Streams {
   // mlkem::CtxState::prepare, which re-zeroes both words after any failed chunk.
   uint32_t* fixc = nullptr;
   int* fixp = nullptr;
-  // batched ML-KEM (one chunk, n > mlkem_small_max()), the handshake driver's expanded-key reuse:
-  // KeyGen writes its sampled matrix A_hat (SampleNTT(rho || x || y), the batched tiled layout,
-  // mlkem_matrix_bytes) to xof_keep instead of the scratch; Decaps of the same keys, same chunk size,
-  // takes it from xof_given and skips its own SampleNTT (A_hat is a function of rho alone).
+  // batched ML-KEM chunks (n > mlkem_small_max()), the KeyGen -> Decaps hand-over of the sampled matrix
+  // A_hat (SampleNTT(rho || x || y), a function of rho alone; mlkem::CtxState's kept region).  Set per
+  // chunk by CtxState::keep_chunk / kept_chunk alone, null where the chunk takes no part in it.
+  // KeyGen writes the chunk's matrix (the batched tiled layout, mlkem_matrix_bytes) to xof_keep instead of
+  // the scratch, and every row's rho, 32 bytes apart, to rho_keep: the row's tag.
   uint64_t* xof_keep = nullptr;
-  const uint64_t* xof_given = nullptr;
+  uint64_t* rho_keep = nullptr;
+  // Decaps of a chunk of the same geometry reads a row's matrix entries from xof_kept where the rho in
+  // its dk equals the row's tag in rho_kept (rows below kept_rows), and samples the other rows as ever.
+  const uint64_t* xof_kept = nullptr;
+  const uint64_t* rho_kept = nullptr;
+  size_t kept_rows = 0;
 };
 
 enum class Op { KEYPAIR, ENCAPS, DECAPS };
+
+// Which chunks of a batched ML-KEM KeyGen of n handshakes, in chunks of `chunk` rows (a multiple of 64),
+// the context keeps the sampled matrix of: whole batched chunks (more than small_max rows; only the last
+// chunk can be shorter), in order, as many as cap_bytes allow.  A kept chunk takes chunk_bytes: its rho
+// tags (32 bytes per row, rounded up to 256) and then its matrix (row_bytes = K^2 384 per row), so chunk
+// i of the region starts at i * chunk_bytes.  Pure arithmetic: the one place that decides what is kept.
+struct KeepPlan {
+  size_t batched, kept, tag_bytes, chunk_bytes, bytes;
+};
+inline KeepPlan mlkem_keep_plan(size_t row_bytes, size_t n, size_t chunk, size_t small_max, size_t cap_bytes) {
+  KeepPlan p{0, 0, 0, 0, 0};
+  if (n == 0 || chunk == 0) return p;
+  const size_t nchunks = (n + chunk - 1) / chunk, last = n - (nchunks - 1) * chunk;
+  p.batched = chunk > small_max ? nchunks - (last > small_max ? 0 : 1) : 0;
+  p.tag_bytes = (32 * chunk + 255) & ~(size_t)255;
+  p.chunk_bytes = p.tag_bytes + row_bytes * chunk;
+  p.kept = std::min(p.batched, cap_bytes / p.chunk_bytes);
+  p.bytes = p.kept * p.chunk_bytes;
+  return p;
+}
+// The cap on the kept region in bytes: QRK_KEEP_MIB (environment, read at every KeyGen; 0 keeps nothing),
+// 8192 MiB by default -- a 2^20 chunk of ML-KEM-1024 is 6.2 GiB, of ML-KEM-768 3.5 GiB.
+size_t mlkem_keep_cap_bytes();
 
 // What a context keeps for ML-KEM alone between calls (a member of qrk_ctx; functions and the
 // invariants they keep in mlkem_batch.cuh, beside rho_source).  The driver calls these under the
@@ -155,9 +185,8 @@ namespace mlkem {
 struct CtxState {
   // Before the chunks of a call of n handshakes (chunks of `chunk`) on S.main: allocates what the call
   // needs on first use, queues the re-zero an earlier failure left owing, and sets S.kg_cnt, S.fixc and
-  // S.fixp.  S.kg_err, S.xof_keep and S.xof_given come in as the caller was asked for them and are
-  // cleared where they do not apply to this call.  scratch: the context's.  On failure *what names
-  // the step.
+  // S.fixp.  S.kg_err comes in as the caller was asked for it and is cleared where it does not apply
+  // to this call.  scratch: the context's.  On failure *what names the step.
   hipError_t prepare(Streams& S, Op op, size_t n, size_t chunk, void* scratch, size_t scratch_bytes,
                      const char** what);
   // a chunk failed after prepare()
@@ -171,7 +200,32 @@ struct CtxState {
   hipError_t fix_words(uint32_t* out, int* parity, const char** what) const;
   hipError_t kg_flags_residue(uint64_t* out) const;
 
+  // ---- the kept region: the sampled matrices of the last batched KeyGen and a 32-byte rho tag per row,
+  // for Decaps of the same keys on this context (layout: KeepPlan).  Public data, a function of the
+  // public rho: wiped with the context's buffers but never for secrecy.  Outputs never depend on the
+  // region, only time does: a Decaps row uses a kept entry only where the rho in its dk equals the tag
+  // KeyGen stored with that entry, and the region is read only while `keep_valid` (host state, never
+  // inferred from device bytes), which every call that writes, fills or frees the region clears first.
+  // A KeyGen of n handshakes in chunks of `chunk` begins: the region is invalid from here.  Sizes it for
+  // plan.kept chunks; before a larger one replaces it quiesce(arg) must wait for the context's last use.
+  // An allocation that fails leaves no region (and no HIP error): the KeyGen keeps nothing.
+  void keep_begin(const AlgInfo& a, size_t n, size_t chunk, size_t cap_bytes, void (*quiesce)(void*), void* arg);
+  // chunk `idx` of that KeyGen: S.xof_keep / S.rho_keep, null when the chunk is not kept
+  void keep_chunk(Streams& S, size_t idx) const;
+  // every chunk of that KeyGen is queued: the region is valid for its kept chunks
+  void keep_commit();
+  // chunk `idx` (m rows) of a Decaps in chunks of `chunk`: S.xof_kept / S.rho_kept / S.kept_rows where the
+  // region is valid and holds a chunk of the same parameter set and geometry, null otherwise
+  void kept_chunk(Streams& S, const AlgInfo& a, size_t chunk, size_t idx, size_t m) const;
+  // the region is invalid from here; its span, for the context's fill and cleanse
+  void keep_invalidate(void** p, size_t* bytes);
+
  private:
+  uint8_t* keep = nullptr;  // the kept region
+  size_t keep_bytes = 0;    // ... as allocated
+  bool keep_valid = false;
+  int keep_k = 0;           // what it holds: the parameter set, and the KeyGen's n, chunk and kept chunks
+  size_t keep_n = 0, keep_chunk_rows = 0, keep_chunks = 0;
   hipError_t kg_rezero(void* scratch, size_t scratch_bytes, hipStream_t st);
   uint32_t* kg_cnt = nullptr;  // single-shot KeyGen arrival counters / flag words (mlkem_kg_flag_words)
   bool kg_dirty = false;       // a pipelined KeyGen failed: a straggler may have set a flag word
