@@ -145,28 +145,39 @@ def keypair_derand(alg: str, coins: bytes) -> tuple[bytes, bytes]:
     r = np.frombuffer(_shake(p, b"\x5f" + seed_se, 4 * n * NBAR), dtype="<u2")
     St = sample(p, r[:n * NBAR]).reshape(NBAR, n)          # S^T, row-major nbar x n
     E = sample(p, r[n * NBAR:]).reshape(n, NBAR)
-    A = gen_a(p, seed_a)
-    Bm = (_mm(A, St.T) + E) & 0xFFFF
-    pk = seed_a + pack(Bm & ((1 << logq) - 1), logq)
+    pk = keygen_from_samples(p, seed_a, St, E)
     pkh = _shake(p, pk, sec)
     sk = s + pk + St.astype("<u2").tobytes() + pkh
     return pk, sk
 
 
-def _encrypt_core(p, pk, seed_se, mu):
+def keygen_from_samples(p, seed_a, St, E):
+    """pk = seedA || Pack(A S + E) from S^T [8][n] and E [n][8] (16-bit two's complement), A = Gen(seedA)."""
+    logq = p["logq"]
+    Bm = (_mm(gen_a(p, seed_a), St.T) + E) & 0xFFFF
+    return seed_a + pack(Bm & ((1 << logq) - 1), logq)
+
+
+def encrypt_from_samples(p, pk, Sp, Ep, Epp, mu):
+    """(B', C) = (S'A + E', S'B + E'' + Encode(mu)) mod q from S' [8][n], E' [8][n], E'' [8][8] (16-bit two's
+    complement), A = Gen(seedA) and B unpacked from pk."""
     n, logq = p["n"], p["logq"]
     qmask = (1 << logq) - 1
-    seed_a = pk[:16]
-    r = np.frombuffer(_shake(p, b"\x96" + seed_se, (2 * n + NBAR) * NBAR * 2), dtype="<u2")
-    Sp = sample(p, r[:n * NBAR]).reshape(NBAR, n)
-    Ep = sample(p, r[n * NBAR:2 * n * NBAR]).reshape(NBAR, n)
-    Epp = sample(p, r[2 * n * NBAR:]).reshape(NBAR, NBAR)
-    A = gen_a(p, seed_a)
+    A = gen_a(p, pk[:16])
     Bp = (_mm(Sp, A) + Ep) & qmask
     Bpk = unpack(pk[16:], n * NBAR, logq).reshape(n, NBAR)
     V = (_mm(Sp, Bpk) + Epp) & qmask
     C = (V + encode(p, mu)) & qmask
     return Bp, C
+
+
+def _encrypt_core(p, pk, seed_se, mu):
+    n = p["n"]
+    r = np.frombuffer(_shake(p, b"\x96" + seed_se, (2 * n + NBAR) * NBAR * 2), dtype="<u2")
+    Sp = sample(p, r[:n * NBAR]).reshape(NBAR, n)
+    Ep = sample(p, r[n * NBAR:2 * n * NBAR]).reshape(NBAR, n)
+    Epp = sample(p, r[2 * n * NBAR:]).reshape(NBAR, NBAR)
+    return encrypt_from_samples(p, pk, Sp, Ep, Epp, mu)
 
 
 def encaps_derand(alg: str, pk: bytes, mu: bytes) -> tuple[bytes, bytes]:

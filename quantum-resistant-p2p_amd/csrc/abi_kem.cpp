@@ -746,4 +746,72 @@ int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t*
   return run_batch(ctx, *a, Op::DECAPS, n, ss, nullptr, ct, sk, nullptr, (hipStream_t)stream, opts);
 }
 
+// The two FrodoKEM forward-path hooks: one chunk on the context's scratch, no chunking (n within the context chunk).
+// The argument checks of qrk_dbg_frodo_decaps_trace, in its order; then the call's scope and the scratch.
+static const AlgInfo* frodo_hook_open(const char* what, CallScope& scope, qrk_ctx* ctx, const char* alg, size_t n,
+                                      bool bufs_ok, hipStream_t st) {
+  if (!ctx) return fail("null context"), nullptr;
+  const AlgInfo* a = resolve(alg);
+  if (!a) return nullptr;
+  if (a->family != Family::FRODO) return fail(std::string("not a FrodoKEM parameter set: ") + alg), nullptr;
+  if (n && !bufs_ok) return fail("null buffer"), nullptr;
+  if (scope.open(ctx, st, CallScope::LOCK | CallScope::ORDER | CallScope::TIMER)) return nullptr;
+  if (n > chunk_for(ctx, *a)) return fail(std::string(what) + ": n exceeds the context chunk"), nullptr;
+  if (n && grow_device(ctx, &ctx->scratch, &ctx->scratch_bytes, ops_of(*a).scratch_bytes(*a, round64(n)), st))
+    return nullptr;
+  return a;
+}
+
+// test hook (qrkem_debug.h): k_fr_sample alone on a caller-chosen stream of 16-bit words
+int qrk_dbg_frodo_sample(qrk_ctx* ctx, const char* alg, int kg, size_t n, const uint16_t* words, int8_t* s8,
+                         int16_t* e16, int16_t* epp16, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  CallScope scope;
+  const AlgInfo* a = frodo_hook_open("frodo_sample", scope, ctx, alg, n, words && s8 && e16 && (kg || epp16), st);
+  if (!a) return -1;
+  if (n == 0) return 0;
+  return hip_done("frodo_sample", frodo_dbg_sample(*a, kg != 0, n, words, s8, e16, epp16, ctx->scratch, st));
+}
+
+// Every value of a device array of n int8 / int16 samples within [-max, max]?  rows x pitch int8 with `used`
+// leading columns per row: the rest (the pad columns) must be zero.  Synchronous (a host copy): -1 on a copy failure.
+static int samples_in_range(const void* dev, size_t rows, size_t pitch, size_t used, bool wide, int max,
+                            hipStream_t st) {
+  std::vector<int16_t> h16(wide ? rows * pitch : 0);
+  std::vector<int8_t> h8(wide ? 0 : rows * pitch);
+  hipError_t e = hipStreamSynchronize(st);
+  if (e == hipSuccess)
+    e = hipMemcpy(wide ? (void*)h16.data() : (void*)h8.data(), dev, rows * pitch * (wide ? 2 : 1), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail("hipMemcpy(samples)", e);
+  for (size_t r = 0; r < rows; ++r)
+    for (size_t c = 0; c < pitch; ++c) {
+      const int v = wide ? h16[r * pitch + c] : h8[r * pitch + c];
+      if (c < used ? (v < -max || v > max) : v != 0) return 1;
+    }
+  return 0;
+}
+
+// test hook (qrkem_debug.h): everything after the sampler, on caller-chosen sample matrices
+int qrk_dbg_frodo_from_samples(qrk_ctx* ctx, const char* alg, int kg, size_t n, const int8_t* s8, const int16_t* e16,
+                               const int16_t* epp16, const uint8_t* in, const uint8_t* mu, uint8_t* out, uint8_t* sk,
+                               void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  CallScope scope;
+  const bool bufs_ok = s8 && e16 && in && out && (kg ? sk != nullptr : epp16 && mu);
+  const AlgInfo* a = frodo_hook_open("frodo_from_samples", scope, ctx, alg, n, bufs_ok, st);
+  if (!a) return -1;
+  if (n == 0) return 0;
+  // the kernels' accumulator bounds and the zero pad of S' hold for the sampler's output only: refuse anything else
+  const int max = frodo_sample_max(*a);
+  const size_t N = (size_t)a->k;
+  int bad = samples_in_range(s8, n * 8, frodo_sample_pitch(*a), N, false, max, st);
+  if (bad == 0) bad = samples_in_range(e16, n, 8 * N, 8 * N, true, max, st);
+  if (bad == 0 && !kg) bad = samples_in_range(epp16, n, 64, 64, true, max, st);
+  if (bad < 0) return -1;
+  if (bad) return fail("frodo_from_samples: a sample outside the parameter set's sampler range (or a nonzero pad column)");
+  hipError_t e = frodo_dbg_from_samples(*a, kg != 0, n, s8, e16, epp16, in, mu, out, sk, ctx->scratch, st);
+  if (e != hipSuccess) return hip_fail("frodo_from_samples", e);
+  return hip_done("hipMemsetAsync(cleanse)", ops_of(*a).cleanse(*a, n, ctx->scratch, st));  // kk holds what seeds held
+}
+
 }  // extern "C"

@@ -57,6 +57,7 @@ struct FP {
   static constexpr int SE_WORDS = (2 * N + NBAR) * NBAR * 2 / 8;  // encaps sampler stream (u64)
   static constexpr int KG_WORDS = 2 * N * NBAR * 2 / 8;           // keygen sampler stream (u64)
   static constexpr int A_BLOCKS = (2 * N + 167) / 168;            // SHAKE128 blocks per row of A
+  static constexpr int SMAX = N_ == 640 ? 12 : (N_ == 976 ? 10 : 6);  // largest |sample| (entries of cdf_sample's table)
 };
 
 template <int N>
@@ -1108,6 +1109,14 @@ void launch_ss(const uint8_t* ct, size_t n, const View<N>& v, uint8_t* ss, hipSt
     QRK_LAUNCH("k_fr_ss", st, k_fr_ss<N>, dim3(blocks_for(n)), dim3(256), 0, st, ct, n, v.kk, ss);
 }
 
+// CDF sampler over the tiled stream of the chunk: Encaps S', E', E''; KeyGen (KG) S^T -> sp8, E -> ep16 as [N][8]
+template <int N, bool KG>
+void launch_sample(const View<N>& v, size_t n, hipStream_t st) {
+  constexpr int W = KG ? FP<N>::KG_WORDS : FP<N>::SE_WORDS;
+  QRK_LAUNCH("k_fr_sample", st, (k_fr_sample<N, KG>), dim3(blocks_for(round64(n) * W)), dim3(256), 0, st, v.raw, n, W,
+             v.sp8, v.ep16, v.epp16);
+}
+
 // partial sums of S'A per handshake that k_fr_pack adds: one per 64-row wave (the SHAKE MFMA
 // kernel), or the column-major AES kernel's row ranges
 template <int N, bool AES>
@@ -1129,6 +1138,31 @@ void launch_sa(const View<N>& v, const uint8_t* seed_base, size_t seed_stride, s
   }
 }
 
+// Encaps: ct = Pack(S'A + E') || Pack(S'B + E'' + Encode(mu)) from the chunk's samples and partial sums; kk = k
+template <int N, bool AES>
+void launch_pack_enc(const View<N>& v, size_t n, const uint8_t* pk, const uint8_t* mu, uint8_t* ct, hipStream_t st) {
+  using P = FP<N>;
+  QRK_LAUNCH("k_fr_pack", st, (k_fr_pack<N, 0, fr_npart<N, AES>()>), dim3((unsigned)n), dim3(256), 0, st, n, pk, (size_t)P::PK, v.sp8,
+             v.ep16, v.epp16, v.part, v.seeds, mu, (size_t)P::MU, ct, nullptr, nullptr, (size_t)0, v.kk);
+}
+
+// KeyGen: B = A S + E (Gen(A) fused, seedA at the head of each pk row) -> v.part as [N][8]
+template <int N, bool AES>
+void launch_as(const View<N>& v, const uint8_t* pk, size_t n, hipStream_t st) {
+  using P = FP<N>;
+  if constexpr (AES) {
+    uint32_t* spair = (uint32_t*)v.raw;  // the sampler stream is consumed by now
+    QRK_LAUNCH("k_fr_kg_spairs", st, k_fr_kg_spairs<N>, dim3(blocks_for(n * N)), dim3(256), 0, st, n, v.sp8, spair);
+    QRK_LAUNCH("k_fr_aes_prep", st, k_fr_aes_prep<N>, dim3(blocks_for(n * (N / 8))), dim3(256), 0, st, pk,
+               (size_t)P::PK, n, v.aesp);
+    QRK_LAUNCH("k_fr_kg_rows_aes", st, k_fr_kg_rows_aes<N>, dim3((unsigned)(n * kg_wgs<N>())), dim3(kg_threads<N>()),
+               0, st, v.aesp, n, spair, v.ep16, v.part);
+  } else {
+    QRK_LAUNCH("k_fr_kg_mm", st, k_fr_kg_mm<N>, dim3((unsigned)(n * P::NWV)), dim3(64), 0, st, pk, n, v.sp8, v.ep16,
+               v.part);
+  }
+}
+
 template <int N, bool AES>
 hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const uint8_t* mu, void* scratch,
                     hipStream_t st) {
@@ -1141,11 +1175,9 @@ hipError_t encaps_t(size_t n, uint8_t* ct, uint8_t* ss, const uint8_t* pk, const
     QRK_LAUNCH("k_fr_front_enc", st, k_fr_front_enc<N>, dim3(blocks_for(n)), dim3(256), 0, st, pk, mu, n, v.seeds);
   }
   launch_se<N>(v, n, 0x96, P::SE_WORDS, st);
-  QRK_LAUNCH("k_fr_sample", st, (k_fr_sample<N, false>), dim3(blocks_for(round64(n) * (P::SE_WORDS))), dim3(256), 0, st,
-             v.raw, n, P::SE_WORDS, v.sp8, v.ep16, v.epp16);
+  launch_sample<N, false>(v, n, st);
   launch_sa<N, AES>(v, pk, P::PK, n, st);
-  QRK_LAUNCH("k_fr_pack", st, (k_fr_pack<N, 0, fr_npart<N, AES>()>), dim3((unsigned)n), dim3(256), 0, st, n, pk, (size_t)P::PK, v.sp8,
-             v.ep16, v.epp16, v.part, v.seeds, mu, (size_t)P::MU, ct, nullptr, nullptr, (size_t)0, v.kk);
+  launch_pack_enc<N, AES>(v, n, pk, mu, ct, st);
   launch_ss<N>(ct, n, v, ss, st);
   return launch_status();
 }
@@ -1159,8 +1191,7 @@ hipError_t decaps_t(size_t n, uint8_t* ss, const uint8_t* ct, const uint8_t* sk,
   QRK_LAUNCH("k_fr_dec_m", st, k_fr_dec_m<N>, dim3((unsigned)n), dim3(256), 0, st, n, ct, sk, v.seeds);
   QRK_LAUNCH("k_fr_g2_dec", st, k_fr_g2_dec<N>, dim3(blocks_for(n)), dim3(256), 0, st, sk, n, v.seeds);
   launch_se<N>(v, n, 0x96, P::SE_WORDS, st);
-  QRK_LAUNCH("k_fr_sample", st, (k_fr_sample<N, false>), dim3(blocks_for(round64(n) * (P::SE_WORDS))), dim3(256), 0, st,
-             v.raw, n, P::SE_WORDS, v.sp8, v.ep16, v.epp16);
+  launch_sample<N, false>(v, n, st);
   launch_sa<N, AES>(v, pk_in_sk, P::SK, n, st);
   QRK_LAUNCH("k_fr_pack", st, (k_fr_pack<N, 1, fr_npart<N, AES>()>), dim3((unsigned)n), dim3(256), 0, st, n, pk_in_sk, (size_t)P::SK,
              v.sp8, v.ep16, v.epp16, v.part, v.seeds, (const uint8_t*)(v.seeds + 12), (size_t)128, nullptr, ct, sk,
@@ -1177,20 +1208,8 @@ hipError_t keypair_t(size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, v
   QRK_LAUNCH("k_fr_kg_front", st, k_fr_kg_front<N>, dim3(blocks_for(n)), dim3(256), 0, st, coins, n, pk, sk,
              v.seeds);
   launch_se<N>(v, n, 0x5F, P::KG_WORDS, st);
-  // S^T -> sp8 ([8][NP] int8), E -> ep16 as [N][8]
-  QRK_LAUNCH("k_fr_sample", st, (k_fr_sample<N, true>), dim3(blocks_for(round64(n) * (P::KG_WORDS))), dim3(256), 0, st,
-             v.raw, n, P::KG_WORDS, v.sp8, v.ep16, v.epp16);
-  if constexpr (AES) {
-    uint32_t* spair = (uint32_t*)v.raw;  // the sampler stream is consumed by now
-    QRK_LAUNCH("k_fr_kg_spairs", st, k_fr_kg_spairs<N>, dim3(blocks_for(n * N)), dim3(256), 0, st, n, v.sp8, spair);
-    QRK_LAUNCH("k_fr_aes_prep", st, k_fr_aes_prep<N>, dim3(blocks_for(n * (N / 8))), dim3(256), 0, st, pk,
-               (size_t)P::PK, n, v.aesp);
-    QRK_LAUNCH("k_fr_kg_rows_aes", st, k_fr_kg_rows_aes<N>, dim3((unsigned)(n * kg_wgs<N>())), dim3(kg_threads<N>()),
-               0, st, v.aesp, n, spair, v.ep16, v.part);
-  } else {
-    QRK_LAUNCH("k_fr_kg_mm", st, k_fr_kg_mm<N>, dim3((unsigned)(n * P::NWV)), dim3(64), 0, st, pk, n, v.sp8, v.ep16,
-               v.part);
-  }
+  launch_sample<N, true>(v, n, st);
+  launch_as<N, AES>(v, pk, n, st);
   QRK_LAUNCH("k_fr_kg_pack", st, k_fr_kg_pack<N>, dim3((unsigned)n), dim3(256), 0, st, n, v.part, v.sp8, pk, sk);
   if (coop_path(n))
     QRK_LAUNCH("k_fr_kg_pkh", st, k_fr_kg_pkh_c<N>, dim3((unsigned)n), dim3(64), 0, st, pk, n, sk);
@@ -1225,7 +1244,105 @@ hipError_t trace_mu_t(size_t n, void* scratch, uint8_t* out, hipStream_t st) {
   return launch_status();
 }
 
+// Tests only (qrk_dbg_frodo_sample): the caller's 16-bit words, spec order [n][4 W], into the tiled stream the
+// sponge kernels write (one thread per u64 = 4 words, little-endian as squeezed).
+__global__ __launch_bounds__(256) void k_fr_dbg_tile(const uint16_t* __restrict__ words, size_t n, int W,
+                                                     uint64_t* __restrict__ raw) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t hs = t / W;
+  const int w = (int)(t % W);
+  if (hs >= n) return;
+  const uint16_t* p = words + t * 4;
+  raw[tidx(hs, w, W)] = (uint64_t)p[0] | (uint64_t)p[1] << 16 | (uint64_t)p[2] << 32 | (uint64_t)p[3] << 48;
+}
+
+// The sampler alone on a chosen stream: the launch of encaps_t / keypair_t on the context's scratch, then its
+// three regions (S' / S^T with the pad columns, E' / E, E'') copied out whole.
+template <int N, bool KG>
+hipError_t dbg_sample_t(size_t n, const uint16_t* words, int8_t* s8, int16_t* e16, int16_t* epp16, void* scratch,
+                        hipStream_t st) {
+  using P = FP<N>;
+  constexpr int W = KG ? P::KG_WORDS : P::SE_WORDS;
+  const View<N> v = carve<N>(scratch, round64(n));
+  QRK_LAUNCH("k_fr_dbg_tile", st, k_fr_dbg_tile, dim3(blocks_for(n * W)), dim3(256), 0, st, words, n, W, v.raw);
+  launch_sample<N, KG>(v, n, st);
+  qrk_chk(hipMemcpyAsync(s8, v.sp8, n * NBAR * P::NP, hipMemcpyDeviceToDevice, st));
+  qrk_chk(hipMemcpyAsync(e16, v.ep16, n * NBAR * N * 2, hipMemcpyDeviceToDevice, st));
+  if (!KG) qrk_chk(hipMemcpyAsync(epp16, v.epp16, n * 64 * 2, hipMemcpyDeviceToDevice, st));
+  return launch_status();
+}
+
+// Everything after the sampler on chosen sample matrices, copied into the scratch regions k_fr_sample fills.
+// Encaps: `in` = pk [n][PK], out = ct [n][CT].  KeyGen: `in` = seedA [n][16], out = pk [n][PK] and, in sk [n][SK],
+// what k_fr_kg_pack writes there (the pk copy and S^T as int16; s and pkh are other kernels').
+template <int N, bool AES>
+hipError_t dbg_from_samples_t(bool kg, size_t n, const int8_t* s8, const int16_t* e16, const int16_t* epp16,
+                              const uint8_t* in, const uint8_t* mu, uint8_t* out, uint8_t* sk, void* scratch,
+                              hipStream_t st) {
+  using P = FP<N>;
+  const View<N> v = carve<N>(scratch, round64(n));
+  qrk_chk(hipMemcpyAsync(v.sp8, s8, n * NBAR * P::NP, hipMemcpyDeviceToDevice, st));
+  qrk_chk(hipMemcpyAsync(v.ep16, e16, n * NBAR * N * 2, hipMemcpyDeviceToDevice, st));
+  if (kg) {
+    qrk_chk(hipMemcpy2DAsync(out, P::PK, in, 16, 16, n, hipMemcpyDeviceToDevice, st));  // seedA heads each pk row
+    launch_as<N, AES>(v, out, n, st);
+    QRK_LAUNCH("k_fr_kg_pack", st, k_fr_kg_pack<N>, dim3((unsigned)n), dim3(256), 0, st, n, v.part, v.sp8, out, sk);
+  } else {
+    qrk_chk(hipMemcpyAsync(v.epp16, epp16, n * 64 * 2, hipMemcpyDeviceToDevice, st));
+    launch_sa<N, AES>(v, in, P::PK, n, st);
+    launch_pack_enc<N, AES>(v, n, in, mu, out, st);
+  }
+  return launch_status();
+}
+
 }  // namespace frodo
+
+int frodo_sample_max(const AlgInfo& a) {
+  switch (a.k) {
+    case 640: return frodo::FP<640>::SMAX;
+    case 976: return frodo::FP<976>::SMAX;
+    case 1344: return frodo::FP<1344>::SMAX;
+  }
+  return 0;
+}
+
+size_t frodo_sample_pitch(const AlgInfo& a) {
+  switch (a.k) {
+    case 640: return frodo::FP<640>::NP;
+    case 976: return frodo::FP<976>::NP;
+    case 1344: return frodo::FP<1344>::NP;
+  }
+  return 0;
+}
+
+hipError_t frodo_dbg_sample(const AlgInfo& a, bool kg, size_t n, const uint16_t* words, int8_t* s8, int16_t* e16,
+                            int16_t* epp16, void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  switch (a.k * 2 + (kg ? 1 : 0)) {
+    case 1280: return frodo::dbg_sample_t<640, false>(n, words, s8, e16, epp16, scratch, st);
+    case 1281: return frodo::dbg_sample_t<640, true>(n, words, s8, e16, epp16, scratch, st);
+    case 1952: return frodo::dbg_sample_t<976, false>(n, words, s8, e16, epp16, scratch, st);
+    case 1953: return frodo::dbg_sample_t<976, true>(n, words, s8, e16, epp16, scratch, st);
+    case 2688: return frodo::dbg_sample_t<1344, false>(n, words, s8, e16, epp16, scratch, st);
+    case 2689: return frodo::dbg_sample_t<1344, true>(n, words, s8, e16, epp16, scratch, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t frodo_dbg_from_samples(const AlgInfo& a, bool kg, size_t n, const int8_t* s8, const int16_t* e16,
+                                  const int16_t* epp16, const uint8_t* in, const uint8_t* mu, uint8_t* out,
+                                  uint8_t* sk, void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  switch (a.k * 2 + (a.aes ? 1 : 0)) {
+    case 1280: return frodo::dbg_from_samples_t<640, false>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+    case 1281: return frodo::dbg_from_samples_t<640, true>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+    case 1952: return frodo::dbg_from_samples_t<976, false>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+    case 1953: return frodo::dbg_from_samples_t<976, true>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+    case 2688: return frodo::dbg_from_samples_t<1344, false>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+    case 2689: return frodo::dbg_from_samples_t<1344, true>(kg, n, s8, e16, epp16, in, mu, out, sk, scratch, st);
+  }
+  return hipErrorInvalidValue;
+}
 
 hipError_t frodo_trace_mu(const AlgInfo& a, size_t n, void* scratch, uint8_t* mu_out, hipStream_t st) {
   if (n == 0) return hipSuccess;

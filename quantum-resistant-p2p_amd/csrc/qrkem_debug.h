@@ -147,6 +147,30 @@ int qrk_dbg_slhdsa_verify_trace(qrk_ctx* ctx, const char* alg, size_t n, const u
 int qrk_dbg_frodo_decaps_trace(qrk_ctx* ctx, const char* alg, size_t n, uint8_t* ss, const uint8_t* ct,
                                const uint8_t* sk, uint8_t* mu_out, void* stream);
 
+// The FrodoKEM sampler alone, on a stream of the caller's choice instead of SHAKE(0x96 / 0x5F || seedSE): n rows
+// of raw 16-bit words in the specification's order, (2 N + 8) 8 per row for Encaps (kg = 0) and 2 N 8 for KeyGen
+// (kg != 0), are laid out as the stream kernels write them and sampled by k_fr_sample<N, KG>, the launch of the
+// public calls, on the context's scratch; its regions are copied out whole.  Encaps: s8 = S' int8 [n][8][NP]
+// (NP = N rounded up to 128: the zeroed pad columns are part of the output), e16 = E' int16 [n][8][N],
+// epp16 = E'' int16 [n][64].  KeyGen: s8 = S^T int8 [n][8][NP], e16 = E int16 [n][N][8], epp16 unused (may be
+// NULL).  Device pointers; n at most the context chunk (one chunk, no chunking).  Through the public calls the
+// words are hash output, which meets a given table boundary about once in 2^15 words and the top entries hardly ever.
+int qrk_dbg_frodo_sample(qrk_ctx* ctx, const char* alg, int kg, size_t n, const uint16_t* words, int8_t* s8,
+                         int16_t* e16, int16_t* epp16, void* stream);
+
+// Everything after the sampler, on sample matrices of the caller's choice in the layout above (pad columns zero).
+// Encaps (kg = 0): in = pk [n][pk bytes], mu [n][len_mu]; Gen(A) fused with S'A (SHAKE or AES as the name says) and
+// k_fr_pack in its Encaps mode write out = ct [n][ct bytes]; sk unused.  KeyGen (kg != 0): in = seedA [n][16];
+// k_fr_kg_spairs where the variant uses it, the A S + E kernel and k_fr_kg_pack write out = seedA || Pack(B)
+// [n][pk bytes] and, into sk [n][sk bytes], the pk copy and S^T as int16 (s and pkh, other kernels' work, are left
+// as the caller had them); epp16 and mu unused.  The launches are those of the public calls.  Every sample must
+// lie in the parameter set's sampler range, |v| <= 12 / 10 / 6 for 640 / 976 / 1344, which is what the kernels'
+// accumulator bounds assume: the hook reads the matrices back first and returns -1 without launching otherwise.
+// Device pointers; n at most the context chunk.  Hash-derived samples have magnitude 2-3 and never fill a tile.
+int qrk_dbg_frodo_from_samples(qrk_ctx* ctx, const char* alg, int kg, size_t n, const int8_t* s8, const int16_t* e16,
+                               const int16_t* epp16, const uint8_t* in, const uint8_t* mu, uint8_t* out, uint8_t* sk,
+                               void* stream);
+
 // qrk_hqc_code_decode (same contract, same limit on n) that also
 // returns the word the decoder is given.  t_out [n][n1 n2 / 8]: the n1 n2 bits of v - u y exactly as
 // the kernel hands them to the Reed-Muller stage, little-endian bytes as in the ciphertext's v.  The

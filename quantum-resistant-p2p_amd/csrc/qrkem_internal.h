@@ -289,6 +289,19 @@ hipError_t frodo_decaps(const AlgInfo& a, size_t n, uint8_t* ss, const uint8_t* 
 // tests only (qrk_dbg_frodo_decaps_trace): after frodo_decaps on the same chunk and scratch and before
 // frodo_cleanse, mu' = Decode(C - B'S) of each handshake to mu_out[n][32] (len_mu bytes, then zeros)
 hipError_t frodo_trace_mu(const AlgInfo& a, size_t n, void* scratch, uint8_t* mu_out, hipStream_t st);
+// tests only (qrk_dbg_frodo_sample): k_fr_sample (kg: its KeyGen instantiation) on the caller's 16-bit words, spec
+// order, laid out as the stream kernels write them; the sampled regions of the scratch copied out whole:
+// s8 [n][8][NP], e16 [n][8 N] and, Encaps only, epp16 [n][64]
+hipError_t frodo_dbg_sample(const AlgInfo& a, bool kg, size_t n, const uint16_t* words, int8_t* s8, int16_t* e16,
+                            int16_t* epp16, void* scratch, hipStream_t st);
+// tests only (qrk_dbg_frodo_from_samples): the launches of frodo_encaps (kg: frodo_keypair) after the sampler, on
+// sample matrices in the layout above.  Encaps: in = pk, out = ct.  KeyGen: in = seedA [n][16], out = pk, and
+// k_fr_kg_pack's part of sk.  The caller has checked the samples against frodo_sample_max / zero pad columns.
+hipError_t frodo_dbg_from_samples(const AlgInfo& a, bool kg, size_t n, const int8_t* s8, const int16_t* e16,
+                                  const int16_t* epp16, const uint8_t* in, const uint8_t* mu, uint8_t* out,
+                                  uint8_t* sk, void* scratch, hipStream_t st);
+int frodo_sample_max(const AlgInfo& a);       // largest |sample| of the parameter set's CDF table: 12 / 10 / 6
+size_t frodo_sample_pitch(const AlgInfo& a);  // NP, the row pitch of S' / S^T in the scratch: n rounded up to 128
 
 hipError_t hqc_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
                        const Streams& st);

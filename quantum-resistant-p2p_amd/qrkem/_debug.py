@@ -36,6 +36,8 @@ HOOKS = {
     "qrk_dbg_mldsa_keyed_sign_mode": (I, [I]),
     "qrk_dbg_slhdsa_verify_trace": (I, _VERIFY_TRACE),
     "qrk_dbg_frodo_decaps_trace": (I, [P, ct.c_char_p, SZ, P, P, P, P, P]),
+    "qrk_dbg_frodo_sample": (I, [P, ct.c_char_p, I, SZ, P, P, P, P, P]),
+    "qrk_dbg_frodo_from_samples": (I, [P, ct.c_char_p, I, SZ, P, P, P, P, P, P, P, P]),
     "qrk_dbg_hqc_decaps_trace": (I, [P, ct.c_char_p, SZ, P, P, P, P, P, P]),
     "qrk_dbg_host_trace": (I, [ct.POINTER(ct.c_longlong)]),
     "qrk_dbg_ss_trace": (I, [ct.POINTER(ct.c_ulonglong)]),

@@ -49,7 +49,7 @@ def kind_of(argtype):
 def test_header_table_and_library_agree():
     from qrkem import _debug
     always, guarded = header_hooks()
-    assert len(always) == 21 and set(guarded) == set(GUARDS.values()) == _debug.TRACE_BUILD
+    assert len(always) == 23 and set(guarded) == set(GUARDS.values()) == _debug.TRACE_BUILD
     # 0. the public header declares no hook: this header is their one home
     assert not [n for n in declared_functions() if n.startswith("qrk_dbg_")]
     # 1. nothing is exported undeclared, nothing is declared unbuilt

@@ -259,6 +259,40 @@ def test_chunks_of_one_call_reuse_each_others_scratch(alg):
         ctx.close()
 
 
+@pytest.mark.parametrize("alg", ["FrodoKEM-976-SHAKE", "FrodoKEM-640-AES"])
+def test_frodo_forward_hooks_after_fill(ctx, alg):
+    """qrk_dbg_frodo_sample and qrk_dbg_frodo_from_samples (both modes), n = 65 on the context under test: the
+    sampler's regions with their zeroed pad columns, ct and pk against frodo_spec (tests/frodo_forward_cases.py)."""
+    import frodo_forward_cases as W
+    import frodo_spec as F
+    import test_gpu_frodo_forward as tf
+    eng, p, n = ctx.kem(alg), F.params(alg), 65
+    gold = tf._gold()[alg]
+
+    def call(seed, dirty):
+        out = {}
+        for kg in (False, True):
+            words = np.roll(np.resize(W.every_word_rows(p, kg, True), (n, W.words_per_row(p, kg))), seed, axis=1)
+            dirty()
+            got = [None if g is None else host(g) for g in tf.run_sample(ctx.lib, eng, kg, dev(words.view(np.int16)))]
+            out["sample", kg] = (got, W.sampler_expected(p, kg, words))
+            inp = W.from_samples_inputs(alg, kg)
+            idx = (np.arange(n) + seed) % len(inp["names"])
+            dirty()
+            got = tf.run_from_samples(ctx.lib, eng, kg, inp, idx)
+            out["rows", kg] = (got[0] if kg else got, idx)
+        return out
+
+    for byte, out in zip(FILLS, through_fills(ctx, call, 0, [5, 11])):
+        for kg in (False, True):
+            got, want = out["sample", kg]
+            for g, w in zip(got, want):
+                assert (g is None and w is None) or np.array_equal(g.reshape(w.shape), w), (alg, hex(byte), kg)
+            rows, idx = out["rows", kg]
+            names = W.from_samples_inputs(alg, kg)["names"]
+            assert W.digests(rows) == [gold["keygen" if kg else "encaps"][names[i]] for i in idx], (alg, hex(byte), kg)
+
+
 # ------------------------------------------------------------------ key sets
 def test_mlkem_key_sets_after_fill(ctx):
     alg, g, n = "ML-KEM-768", 5, 65

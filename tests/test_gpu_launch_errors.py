@@ -295,6 +295,40 @@ def frodo_decaps_trace(lib, ctx):
                                                   mu.data_ptr(), _stream()), [ss, mu]
 
 
+def frodo_sample(kg):
+    def build(lib, ctx):
+        import frodo_forward_cases as W
+        import frodo_spec as F
+        alg, n = "FrodoKEM-640-SHAKE", 64
+        p = F.params(alg)
+        words = _dev(np.resize(W.every_word_rows(p, kg, True), (n, W.words_per_row(p, kg))).view(np.int16))
+        outs = [_out(n, 8, W.pitch(p["n"])), _out(n, 8 * p["n"], dtype=torch.int16)]  # int8 samples as bytes
+        outs += [] if kg else [_out(n, 64, dtype=torch.int16)]
+        epp = None if kg else outs[2].data_ptr()
+        return lambda: lib.qrk_dbg_frodo_sample(ctx, alg.encode(), int(kg), n, words.data_ptr(), outs[0].data_ptr(),
+                                                outs[1].data_ptr(), epp, _stream()), outs
+    return build
+
+
+def frodo_from_samples(alg, kg):
+    def build(lib, ctx):
+        import frodo_forward_cases as W
+        import frodo_spec as F
+        n, p, inp = 64, F.params(alg), W.from_samples_inputs(alg, kg)
+        idx = W.tiled(len(inp["names"]), n)
+        s8, e16 = _dev(inp["s8"][idx]), _dev(inp["e16"][idx])
+        if kg:
+            src, outs = _dev(inp["seedA"][idx]), [_out(n, p["pk"]), _out(n, p["sk"])]
+            return lambda: lib.qrk_dbg_frodo_from_samples(ctx, alg.encode(), 1, n, s8.data_ptr(), e16.data_ptr(), None,
+                                                          src.data_ptr(), None, outs[0].data_ptr(), outs[1].data_ptr(),
+                                                          _stream()), outs
+        epp, pk, mu, outs = _dev(inp["epp16"][idx]), _dev(inp["pk"][idx]), _dev(inp["mu"][idx]), [_out(n, p["ct"])]
+        return lambda: lib.qrk_dbg_frodo_from_samples(ctx, alg.encode(), 0, n, s8.data_ptr(), e16.data_ptr(),
+                                                      epp.data_ptr(), pk.data_ptr(), mu.data_ptr(), outs[0].data_ptr(),
+                                                      None, _stream()), outs
+    return build
+
+
 def dbg_hook(name, fixed_len):
     def build(lib, ctx):
         n = 64
@@ -317,6 +351,12 @@ CASES.update({
     f"sig_sign-{SLH}-{SLH_ROWS}": slh_sign,
     "dbg_poly1305": dbg_hook("qrk_dbg_poly1305_batch", 32), "dbg_ghash": dbg_hook("qrk_dbg_ghash_batch", 16),
     "dbg_frodo_decaps_trace-FrodoKEM-640-SHAKE-64": frodo_decaps_trace,
+    "dbg_frodo_sample-encaps-FrodoKEM-640-SHAKE-64": frodo_sample(False),
+    "dbg_frodo_sample-keygen-FrodoKEM-640-SHAKE-64": frodo_sample(True),
+    "dbg_frodo_from_samples-encaps-FrodoKEM-640-SHAKE-64": frodo_from_samples("FrodoKEM-640-SHAKE", False),
+    "dbg_frodo_from_samples-keygen-FrodoKEM-640-SHAKE-64": frodo_from_samples("FrodoKEM-640-SHAKE", True),
+    "dbg_frodo_from_samples-encaps-FrodoKEM-640-AES-64": frodo_from_samples("FrodoKEM-640-AES", False),
+    "dbg_frodo_from_samples-keygen-FrodoKEM-640-AES-64": frodo_from_samples("FrodoKEM-640-AES", True),
 })
 for _alg in ("AES-256-GCM", "ChaCha20-Poly1305"):
     CASES[f"aead_seal-{_alg}"] = aead_seal(_alg)
