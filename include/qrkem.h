@@ -485,6 +485,43 @@ int qrk_mlkem_encaps_keyed_batch(qrk_ctx *ctx, const qrk_mlkem_keyset *ks, size_
 int qrk_mlkem_decaps_keyed_batch(qrk_ctx *ctx, const qrk_mlkem_keyset *ks, size_t n, const uint32_t *key_index,
                                  uint8_t *ss, const uint8_t *ct, int32_t *status, void *stream);
 
+/* FrodoKEM key sets: the same contract for the six FrodoKEM names (640 / 976 / 1344, SHAKE and AES), where the key
+ * alone decides most of a row's cost: qrk_kem_encaps_batch / qrk_kem_decaps_batch regenerate the N x N matrix A from
+ * seedA (FrodoKEM-640: 5,120 Keccak permutations, or 51,200 AES blocks) and hash the whole public key for every row.
+ * A key set generates A once per key, and the keyed calls compute S'A for all rows that share a key as one integer
+ * matrix product against the stored A.
+ *
+ * Load, free and info are qrk_mlkem_pubkeys_load .. qrk_mlkem_keyset_free word for word, with these differences.  The
+ * name check accepts the six FrodoKEM names (an ML-KEM or HQC name: -1 with "these key sets are FrodoKEM only", any
+ * other with "unsupported KEM").  Nothing about a key is checked at load (FrodoKEM has no key validity check).  A
+ * set holds, per key, A as two planes of int8 limbs (A = 256 hi + lo, 2 N^2 bytes), B unpacked to 16-bit words
+ * (16 N) and pkh (32); a secret set adds S^T (16 N) and s (32), which are secret.  That is 829,472 / 1,920,800 /
+ * 3,634,208 bytes per public key and 839,744 / 1,936,448 / 3,655,744 per secret key for FrodoKEM-640 / 976 / 1344,
+ * plus at most 1.5 KiB of alignment and slack per set: 64 FrodoKEM-1344 keys are 233 MB.  A load whose allocation
+ * fails is refused with a message that names the size; nothing is left allocated.
+ * qrk_frodo_keyset_info: out = { g, parameter set (0 .. 5 = 640-SHAKE, 640-AES, 976-SHAKE, 976-AES, 1344-SHAKE,
+ * 1344-AES), 1 if secret, device bytes held }.
+ *
+ * Encaps / Decaps under a set are qrk_mlkem_encaps_keyed_batch / qrk_mlkem_decaps_keyed_batch word for word: the same
+ * arguments (coins: mu, len_mu bytes per row), the same checks in the same order, refused rows (index >= g: status
+ * -1, an all-zero ct / ss row, and the row takes no part in the matrix product) and results byte for byte those of
+ * qrk_kem_encaps_batch / qrk_kem_decaps_batch for the same keys and coins.  status is 0 for every other row (Decaps
+ * rejects implicitly).  Rows are grouped by key on the device (key_index is public); results do not depend on the
+ * order of rows or on how keys interleave.  The scratch grows by 46.5 / 71.1 / 97.7 KB per row (64 N + 8 NP + 420
+ * bytes, NP = N rounded up to 128; the per-row calls take 150 / 323 / 552 KB) plus 16 bytes per key, and the secret
+ * records (seedSE, k, mu', the hashed key) are zeroed behind every chunk. */
+typedef struct qrk_frodo_keyset qrk_frodo_keyset;
+int qrk_frodo_pubkeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *pk, qrk_frodo_keyset **out,
+                           void *stream);
+int qrk_frodo_seckeys_load(qrk_ctx *ctx, const char *alg, size_t g, const uint8_t *sk, qrk_frodo_keyset **out,
+                           void *stream);
+int qrk_frodo_keyset_info(const qrk_frodo_keyset *ks, size_t out[4]);
+void qrk_frodo_keyset_free(qrk_frodo_keyset *ks);
+int qrk_frodo_encaps_keyed_batch(qrk_ctx *ctx, const qrk_frodo_keyset *ks, size_t n, const uint32_t *key_index,
+                                 uint8_t *ct, uint8_t *ss, const uint8_t *coins, int32_t *status, void *stream);
+int qrk_frodo_decaps_keyed_batch(qrk_ctx *ctx, const qrk_frodo_keyset *ks, size_t n, const uint32_t *key_index,
+                                 uint8_t *ss, const uint8_t *ct, int32_t *status, void *stream);
+
 /* Wire format: standard base64 (RFC 4648 section 4, '=' padding), the encoding the reference
  * puts every KEM payload in before JSON framing (messaging.py:607 public key, :852-853
  * ciphertext and responder key; decoded at :829 with base64.b64decode).  Device pointers,

@@ -1,5 +1,5 @@
 // Internal host-side interface between the C-ABI (abi_*.cpp) and the kernel
-// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, mlkem_keyed.hip, frodo.hip, hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
+// launchers (mlkem.hip and its path files mlkem_batch.cuh, mlkem_one.cuh, mlkem_kg.cuh, mlkem_keyed.hip, frodo.hip (frodo_kernels.cuh), frodo_keyed.hip (frodo_keyed.cuh), hqc.hip, util.hip, hkdf.hip, wire.hip, aead.hip, aead_long.hip,
 // mldsa.hip, mldsa_sign.hip, mldsa_keyed.hip, slhdsa.hip, slhdsa_sign.hip).  Not part of the public ABI.
 // The exported test hooks (qrk_dbg_*) are declared in qrkem_debug.h and bound for ctypes in qrkem/_debug.py.
 #pragma once
@@ -302,6 +302,37 @@ hipError_t frodo_dbg_from_samples(const AlgInfo& a, bool kg, size_t n, const int
                                   uint8_t* sk, void* scratch, hipStream_t st);
 int frodo_sample_max(const AlgInfo& a);       // largest |sample| of the parameter set's CDF table: 12 / 10 / 6
 size_t frodo_sample_pitch(const AlgInfo& a);  // NP, the row pitch of S' / S^T in the scratch: n rounded up to 128
+
+// FrodoKEM key sets (frodo_keyed.hip): g keys expanded once into one device allocation of frodo_keyset_bytes, and
+// Encaps / Decaps of n rows that name their key by index.  FrodoKeys is the view of that allocation
+// (frodo_keyset_view; device pointers): A as two int8 limb planes per key, [g][lo, hi][N columns][N rows]
+// (A = 256 hi + lo); B u16 [g][N][8]; pkh [g][32]; a secret set adds S^T int16 [g][8][N] and s [g][32] (both
+// secret).  key_index [n] (device; NULL: every row uses key 0) is checked against g on the device before any address
+// is formed from it: a row with an index >= g joins no tile of the product, gets status -1 and an all-zero ct / ss
+// row.  Everything else as frodo_encaps / frodo_decaps, whose bytes these return; status is written for every row.
+// The scratch (frodo_keyed_scratch_bytes, which depends on g for the grouping tables) holds the per-row call's
+// regions with whole sums of S'A in place of the per-wave partials; frodo_keyed_cleanse zeroes seeds | kk after
+// every chunk.
+struct FrodoKeys {
+  uint32_t g = 0;
+  const int8_t* planes = nullptr;
+  const uint16_t* B = nullptr;
+  const uint64_t* pkh = nullptr;
+  const int16_t* St = nullptr;
+  const uint64_t* s = nullptr;
+};
+size_t frodo_keyset_bytes(const AlgInfo& a, bool secret, size_t g);
+FrodoKeys frodo_keyset_view(const AlgInfo& a, bool secret, size_t g, void* mem);
+// keys: pk [g][pk] or sk [g][sk]; mem: frodo_keyset_bytes, every byte of it is written
+hipError_t frodo_keyset_expand(const AlgInfo& a, bool secret, size_t g, const uint8_t* keys, void* mem,
+                               hipStream_t st);
+int frodo_keyed_tile_rows();  // same-key rows per tile of the product kernel
+size_t frodo_keyed_scratch_bytes(const AlgInfo& a, size_t chunk, size_t g);
+hipError_t frodo_keyed_cleanse(const AlgInfo& a, size_t n, size_t g, void* scratch, hipStream_t st);
+hipError_t frodo_encaps_keyed(const AlgInfo& a, const FrodoKeys& ks, size_t n, const uint32_t* key_index, uint8_t* ct,
+                              uint8_t* ss, const uint8_t* coins, int32_t* status, void* scratch, const Streams& s);
+hipError_t frodo_decaps_keyed(const AlgInfo& a, const FrodoKeys& ks, size_t n, const uint32_t* key_index, uint8_t* ss,
+                              const uint8_t* ct, int32_t* status, void* scratch, const Streams& s);
 
 hipError_t hqc_keypair(const AlgInfo& a, size_t n, uint8_t* pk, uint8_t* sk, const uint8_t* coins, void* scratch,
                        const Streams& st);

@@ -26,7 +26,8 @@ _SIGNATURES = ("SignatureAlgorithm", "MLDSASignature", "MLDSASigner", "MLDSAKeyS
 
 
 # ML-KEM key sets (batch.py over mlkem_keyed.hip): BatchKEM.load_public_keys / encaps_keyed and their secret halves
-_BATCH = ("BatchKEM", "MLKEMKeySet")
+# ... and FrodoKEM key sets (frodo_keyed.hip): FrodoBatchKEM, a BatchKEM whose keyed methods take a FrodoKeySet
+_BATCH = ("BatchKEM", "MLKEMKeySet", "FrodoBatchKEM", "FrodoKeySet")
 
 
 def __getattr__(name: str):

@@ -86,6 +86,12 @@ def _bind(lib: ct.CDLL) -> ct.CDLL:
         "qrk_mlkem_keyset_free": (None, [P]),
         "qrk_mlkem_encaps_keyed_batch": (ct.c_int, [P, P, SZ, P, P, P, P, P, P]),
         "qrk_mlkem_decaps_keyed_batch": (ct.c_int, [P, P, SZ, P, P, P, P, P]),
+        "qrk_frodo_pubkeys_load": (ct.c_int, [P, ct.c_char_p, SZ, P, ct.POINTER(P), P]),
+        "qrk_frodo_seckeys_load": (ct.c_int, [P, ct.c_char_p, SZ, P, ct.POINTER(P), P]),
+        "qrk_frodo_keyset_info": (ct.c_int, [P, ct.POINTER(SZ)]),
+        "qrk_frodo_keyset_free": (None, [P]),
+        "qrk_frodo_encaps_keyed_batch": (ct.c_int, [P, P, SZ, P, P, P, P, P, P]),
+        "qrk_frodo_decaps_keyed_batch": (ct.c_int, [P, P, SZ, P, P, P, P, P]),
         "qrk_base64_encode_batch": (ct.c_int, [P, SZ, P, SZ, P, P]),
         "qrk_base64_decode_batch": (ct.c_int, [P, SZ, P, SZ, P, P, P]),
         "qrk_ctx_profile": (ct.c_int, [P, ct.c_int]),

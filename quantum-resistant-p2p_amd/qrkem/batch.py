@@ -70,12 +70,9 @@ def _as_host(x, width: int) -> np.ndarray:
     return a
 
 
-class MLKEMKeySet:
-    """g ML-KEM keys expanded once on the device (``qrk_mlkem_pubkeys_load`` / ``qrk_mlkem_seckeys_load``,
-    mlkem_keyed.hip): what :meth:`BatchKEM.encaps_keyed` and :meth:`BatchKEM.decaps_keyed` index into.  Made by
-    :meth:`BatchKEM.load_public_keys` / :meth:`BatchKEM.load_secret_keys`; owns the handle and is a context
-    manager.  A secret set holds the dk bytes in device memory until :meth:`close`, which zeroes them (the
-    library synchronises the device first)."""
+class _KeySet:
+    """What the key-set classes share: the handle of a set loaded on the device, its description, and its release."""
+    _INFO = _FREE = ""  # the library's info / free call of the family
 
     def __init__(self, handle, alg: str, g: int, secret: bool, device: int = 0):
         self._handle = handle
@@ -90,18 +87,18 @@ class MLKEMKeySet:
 
     @property
     def device_bytes(self) -> int:
-        """Bytes of device memory the set holds (``qrk_mlkem_keyset_info``); 0 once closed."""
+        """Bytes of device memory the set holds (the library's ``*_keyset_info``); 0 once closed."""
         if self.closed:
             return 0
         out = (ct.c_size_t * 4)()
-        if LIB.qrk_mlkem_keyset_info(self._handle, out) != 0:
+        if getattr(LIB, self._INFO)(self._handle, out) != 0:
             raise RuntimeError(last_error())
         return int(out[3])
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
         if h:
-            LIB.qrk_mlkem_keyset_free(h)
+            getattr(LIB, self._FREE)(h)
 
     def __enter__(self):
         return self
@@ -118,7 +115,24 @@ class MLKEMKeySet:
 
     def __repr__(self) -> str:
         kind = "secret" if self.secret else "public"
-        return f"<MLKEMKeySet {self.alg} {kind} g={self.g}{' closed' if self.closed else ''}>"
+        return f"<{type(self).__name__} {self.alg} {kind} g={self.g}{' closed' if self.closed else ''}>"
+
+
+class MLKEMKeySet(_KeySet):
+    """g ML-KEM keys expanded once on the device (``qrk_mlkem_pubkeys_load`` / ``qrk_mlkem_seckeys_load``,
+    mlkem_keyed.hip): what :meth:`BatchKEM.encaps_keyed` and :meth:`BatchKEM.decaps_keyed` index into.  Made by
+    :meth:`BatchKEM.load_public_keys` / :meth:`BatchKEM.load_secret_keys`; owns the handle and is a context
+    manager.  A secret set holds the dk bytes in device memory until :meth:`close`, which zeroes them (the
+    library synchronises the device first)."""
+    _INFO, _FREE = "qrk_mlkem_keyset_info", "qrk_mlkem_keyset_free"
+
+
+class FrodoKeySet(_KeySet):
+    """g FrodoKEM keys expanded once on the device (``qrk_frodo_pubkeys_load`` / ``qrk_frodo_seckeys_load``,
+    frodo_keyed.hip): A as int8 limb planes, B unpacked and pkh per key, and S^T and s in a secret set.  Made by
+    :meth:`FrodoBatchKEM.load_public_keys` / :meth:`FrodoBatchKEM.load_secret_keys`; owns the handle and is a
+    context manager.  A secret set holds S^T and s in device memory until :meth:`close`, which zeroes them."""
+    _INFO, _FREE = "qrk_frodo_keyset_info", "qrk_frodo_keyset_free"
 
 
 class BatchKEM:
@@ -243,11 +257,19 @@ class BatchKEM:
         return (ss, st) if return_status else ss
 
     # ------------------------------------------------------------------ key sets (ML-KEM)
+    _KEYSET = MLKEMKeySet    # what the keyed methods take and the loaders make ...
+    _KEYED_PREFIX = "qrk_mlkem_"  # ... and the family of library calls behind them
+
+    def _keyed_call(self, name: str):
+        """The library's `name` call of this class's key sets: pubkeys_load, seckeys_load, encaps_keyed_batch,
+        decaps_keyed_batch."""
+        return getattr(LIB, self._KEYED_PREFIX + name)
+
     def _keyed_only(self) -> None:
         if not self.alg.startswith("ML-KEM-"):
             raise ValueError(f"key sets are ML-KEM only: {self.alg} has none (use encaps / decaps)")
 
-    def _load_keys(self, keys, width: int, secret: bool) -> MLKEMKeySet:
+    def _load_keys(self, keys, width: int, secret: bool):
         self._keyed_only()
         what = "secret" if secret else "public"
         if not _is_dev(keys):
@@ -257,10 +279,10 @@ class BatchKEM:
         if g == 0:
             raise ValueError(f"a key set holds at least one {what} key")
         h = ct.c_void_p()
-        load = LIB.qrk_mlkem_seckeys_load if secret else LIB.qrk_mlkem_pubkeys_load
+        load = self._keyed_call("seckeys_load" if secret else "pubkeys_load")
         self._check(load(self._ctx, self._name, g, _dptr(keys), ct.byref(h), self._stream()), "key set load")
         torch.cuda.current_stream(self.device).synchronize()  # the set is ready on every stream; `keys` may go
-        return MLKEMKeySet(h, self.alg, g, secret, self.device)
+        return self._KEYSET(h, self.alg, g, secret, self.device)
 
     def load_public_keys(self, pk) -> MLKEMKeySet:
         """A key set of the g encapsulation keys pk [g, pk_len] (a device tensor, numpy array or list of bytes):
@@ -272,8 +294,9 @@ class BatchKEM:
         return self._load_keys(sk, self.sk_len, True)
 
     def _keyed_args(self, keyset, secret: bool, key_index, n: int):
-        if not isinstance(keyset, MLKEMKeySet):
-            raise ValueError("keyset must be an MLKEMKeySet")
+        if not isinstance(keyset, self._KEYSET):
+            article = "an" if self._KEYSET is MLKEMKeySet else "a"
+            raise ValueError(f"keyset must be {article} {self._KEYSET.__name__}")
         if keyset.alg != self.alg:
             raise ValueError(f"the key set holds {keyset.alg} keys, this object is {self.alg}")
         if keyset.secret and not secret:
@@ -320,11 +343,10 @@ class BatchKEM:
             _check_dev(coins, self.enc_coins, "encaps coins", n)
         c, ss = self._empty(n, self.ct_len), self._empty(n, self.ss_len)
         st = torch.empty((n,), dtype=torch.int32, device=dev) if return_status else None
-        self._check(LIB.qrk_mlkem_encaps_keyed_batch(self._ctx, keyset._handle, n,
-                                                     _kptr(key_index), _dptr(c), _dptr(ss),
-                                                     _dptr(coins) if coins is not None else None,
-                                                     _dptr(st) if st is not None else None, self._stream()),
-                    "encaps_keyed")
+        encaps = self._keyed_call("encaps_keyed_batch")
+        self._check(encaps(self._ctx, keyset._handle, n, _kptr(key_index), _dptr(c), _dptr(ss),
+                           _dptr(coins) if coins is not None else None, _dptr(st) if st is not None else None,
+                           self._stream()), "encaps_keyed")
         return (c, ss, st) if return_status else (c, ss)
 
     def decaps_keyed(self, keyset, ct_, key_index=None, return_status: bool = False):
@@ -338,9 +360,9 @@ class BatchKEM:
         key_index = self._keyed_args(keyset, True, key_index, n)
         ss = self._empty(n, self.ss_len)
         st = torch.empty((n,), dtype=torch.int32, device=ct_.device) if return_status else None
-        self._check(LIB.qrk_mlkem_decaps_keyed_batch(self._ctx, keyset._handle, n, _kptr(key_index), _dptr(ss),
-                                                     _dptr(ct_), _dptr(st) if st is not None else None,
-                                                     self._stream()), "decaps_keyed")
+        decaps = self._keyed_call("decaps_keyed_batch")
+        self._check(decaps(self._ctx, keyset._handle, n, _kptr(key_index), _dptr(ss), _dptr(ct_),
+                           _dptr(st) if st is not None else None, self._stream()), "decaps_keyed")
         return (ss, st) if return_status else ss
 
     @property
@@ -446,3 +468,44 @@ class BatchKEM:
         self._check(bind().qrk_dbg_hqc_decaps_trace(self._ctx, self._name, n, _dptr(sk), _dptr(ct_), _dptr(t),
                                                     _dptr(syms), _dptr(mp), self._stream()), "hqc_decaps_trace")
         return t, syms, mp
+
+
+class FrodoBatchKEM(BatchKEM):
+    """:class:`BatchKEM` for a FrodoKEM name, with key sets: the four keyed methods of :class:`BatchKEM` (same
+    parameter lists, same wrapper checks, same host and device inputs) over ``qrk_frodo_*`` and
+    :class:`FrodoKeySet`.  Gen(A), the unpacking of B and H(pk) run once per key at load; a keyed call computes S'A
+    of all rows that share a key as one integer matrix product against the stored A.  Results are byte for byte
+    those of :meth:`encaps` / :meth:`decaps` for the same keys and mu.  :class:`BatchKEM` itself has key sets for
+    ML-KEM only."""
+    _KEYSET = FrodoKeySet
+    _KEYED_PREFIX = "qrk_frodo_"
+
+    def __init__(self, alg: str, device: int = 0, chunk: Optional[int] = None):
+        if not str(alg).startswith("FrodoKEM-"):
+            raise ValueError(f"FrodoBatchKEM is for FrodoKEM names: {alg} is none (use BatchKEM)")
+        super().__init__(alg, device, chunk)
+
+    def _keyed_only(self) -> None:
+        if not self.alg.startswith("FrodoKEM-"):
+            raise ValueError(f"FrodoBatchKEM is for FrodoKEM names: {self.alg} is none (use BatchKEM)")
+
+    def load_public_keys(self, pk) -> FrodoKeySet:
+        """A key set of the g public keys pk [g, pk_len] (a device tensor, numpy array or list of bytes): Gen(A),
+        the unpacking of B and pkh = H(pk) run once per key here and never again per row."""
+        return self._load_keys(pk, self.pk_len, False)
+
+    def load_secret_keys(self, sk) -> FrodoKeySet:
+        """A key set of the g secret keys sk [g, sk_len]: Gen(A) runs once per key here; S^T, s and pkh are copied."""
+        return self._load_keys(sk, self.sk_len, True)
+
+    def encaps_keyed(self, keyset, key_index=None, n: Optional[int] = None, coins=None, return_status: bool = False):
+        """Encaps of n rows under a public key set: row i uses key ``key_index[i]`` (None: key 0 of a set of one);
+        ``coins`` is mu [n, enc_coins] or None (OS CSPRNG).  Returns device (ct, ss) (+ status int32[n]: -1 and a
+        zero ct / ss row where the index is outside the set): byte for byte what :meth:`encaps` returns."""
+        return super().encaps_keyed(keyset, key_index, n, coins, return_status)
+
+    def decaps_keyed(self, keyset, ct_, key_index=None, return_status: bool = False):
+        """Decaps of the rows ct [n, ct_len] under a secret key set.  Returns device ss [n, ss_len] (+ status
+        int32[n]: 0, or -1 with a zero ss row where the index is outside the set; an invalid ciphertext is rejected
+        implicitly with the key's s, status 0): byte for byte what :meth:`decaps` returns."""
+        return super().decaps_keyed(keyset, ct_, key_index, return_status)
