@@ -33,6 +33,7 @@ import abc
 import ctypes as ct
 import logging
 import os
+import threading
 from typing import Tuple
 
 import numpy as np
@@ -91,14 +92,18 @@ class _BatchVerifier(SignatureAlgorithm):
         self.device = device
         self.public_key_size, self.secret_key_size, self.signature_size = sig_sizes(self.variant)
         self._ctx = None
+        self._ctx_lock = threading.Lock()
 
     def _context(self):
-        if self._ctx is None:
-            h = ct.c_void_p()
-            if LIB.qrk_ctx_create(ct.byref(h), self.device) != 0:
-                raise RuntimeError(f"qrkem: cannot create a context on device {self.device}: {last_error()}")
-            self._ctx = h
-        return self._ctx
+        # one context per object, whichever thread asks first: ctypes drops the GIL inside qrk_ctx_create, so
+        # without the lock two first calls would each create one and the loser's would never be destroyed
+        with self._ctx_lock:
+            if self._ctx is None:
+                h = ct.c_void_p()
+                if LIB.qrk_ctx_create(ct.byref(h), self.device) != 0:
+                    raise RuntimeError(f"qrkem: cannot create a context on device {self.device}: {last_error()}")
+                self._ctx = h
+            return self._ctx
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):

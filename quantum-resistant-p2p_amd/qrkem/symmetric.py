@@ -18,6 +18,7 @@ from __future__ import annotations
 import abc
 import ctypes as ct
 import os
+import threading
 from typing import Optional, Sequence, Union
 
 import numpy as np
@@ -234,6 +235,7 @@ class _GpuAEAD(SymmetricAlgorithm):
     def __init__(self, device: int = 0):
         self.device = device
         self._ctx = None
+        self._ctx_lock = threading.Lock()
 
     def _long(self, longest: Optional[int], n: int) -> Optional[int]:
         """The ``max_len`` to call the long pair with, or None for the one-lane pair."""
@@ -255,12 +257,15 @@ class _GpuAEAD(SymmetricAlgorithm):
         return os.urandom(self.key_size)
 
     def _context(self):
-        if self._ctx is None:
-            h = ct.c_void_p()
-            if LIB.qrk_ctx_create(ct.byref(h), self.device) != 0:
-                raise RuntimeError(f"qrkem: cannot create a context on device {self.device}: {last_error()}")
-            self._ctx = h
-        return self._ctx
+        # one context per object, whichever thread asks first: ctypes drops the GIL inside qrk_ctx_create, so
+        # without the lock two first calls would each create one and the loser's would never be destroyed
+        with self._ctx_lock:
+            if self._ctx is None:
+                h = ct.c_void_p()
+                if LIB.qrk_ctx_create(ct.byref(h), self.device) != 0:
+                    raise RuntimeError(f"qrkem: cannot create a context on device {self.device}: {last_error()}")
+                self._ctx = h
+            return self._ctx
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
